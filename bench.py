@@ -14,7 +14,15 @@ Reference CPU baseline: 0.76 ZMW/s on one 16-vCPU shard
 (docs/quick_start.md:315-320).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-size B]
+                       [--dump-outputs DIR] [--full]
 Under torchrun, reads RANK/LOCAL_RANK/WORLD_SIZE from the environment.
+
+A plain run sets up, warms up, times the K steps and prints the result
+line. --full adds the untimed native-vs-torch output audit at the benched
+batch (config.native_vs_torch_agree*). --dump-outputs DIR writes the base
+and quality calls of the last timed step as DIR/bases.npy and
+DIR/quals.npy (float32); inputs and weights are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -199,6 +207,12 @@ def main():
     ap.add_argument("--shards", type=int, default=0,
                     help="pipeline mode: worker processes (one per GPU "
                     "via modulo; default = visible GPU count)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed native-vs-torch output "
+                    "audit at the benched batch and report it in config")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as "
+                    "DIR/bases.npy and DIR/quals.npy (float32)")
     args = ap.parse_args()
 
     if args.pipeline:
@@ -328,10 +342,11 @@ def main():
     # Output-validity audit: the timed number only counts if the native
     # path computes the same calls as the torch reference AT THIS BATCH
     # (a large-batch corruption was observed on the native path —
-    # tests/test_gpu_large_batch.py). Reported in the JSON, not timed.
+    # tests/test_gpu_large_batch.py). Reported in the JSON, not timed;
+    # only with --full.
     native_agree = None
     native_agree_confident = None
-    if have_cuda and runner.native:
+    if args.full and have_cuda and runner.native:
         with torch.no_grad():
             # Full-batch native forward (the corruption is batch-size
             # dependent), torch reference on head+tail slices. Raw
@@ -363,12 +378,18 @@ def main():
 
         dist.barrier()
 
+    last_out = None
     t0 = time.perf_counter()
     for i in range(args.steps):
-        one_step(i)
+        last_out = one_step(i)
     if have_cuda:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and last_out is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in zip(("bases", "quals"), last_out):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"),
+                    t.numpy().astype(np.float32))
     if distributed:
         import torch.distributed as dist
 

@@ -161,7 +161,11 @@ def _dp_worker(rank, world, train_file, out_dir, port):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     from deepconsensus_amd.models import train as train_lib
+    from deepconsensus_amd.parallel import comm
 
+    # CPU tensors need gloo; the default backend is nccl wherever a GPU
+    # is visible.
+    assert comm.init_distributed(backend="gloo") == (rank, world)
     params = _tiny_params(train_file, model="fc")
     train_lib.train_model(out_dir, params, device="cpu", eval_every=100,
                           limit_steps=2)

@@ -119,8 +119,12 @@ def test_train_writes_tensorboard_events(tmp_path):
 
 def test_enable_tuned_gemms_cpu_noop(monkeypatch):
     """On CPU the tuned-GEMM loader is a no-op returning False."""
+    import torch
+
     import deepconsensus_amd.utils.tuned_gemm as tg
 
+    # The CPU case, also when the suite runs on a GPU machine.
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     monkeypatch.setattr(tg, "_ENABLED", None)
     assert tg.enable_tuned_gemms() is False
     # Disabled via env as well.
