@@ -75,6 +75,12 @@ def _run_main(argv: List[str]) -> None:
     ap.add_argument("--end_after_stage", default="full",
                     choices=[s.name.lower() for s in qi.DebugStage],
                     help="stop after this stage (debug/runtime testing)")
+    ap.add_argument("--stitch_mode", default=None,
+                    choices=list(qi.STITCH_MODES),
+                    help="window stitcher: serial (in-process Python), "
+                    "pool (process pool, FASTQ only) or device (gap "
+                    "compaction on the GPU; numpy on CPU). Default: the "
+                    "DC_STITCH_MODE environment variable, else serial")
     ap.add_argument("--use_only_gpu_index", type=int, default=None,
                     help="pin inference to this GPU index "
                     "(shorthand for --device cuda:N)")
@@ -100,6 +106,7 @@ def _run_main(argv: List[str]) -> None:
         ins_trim=args.ins_trim,
         use_ccs_smart_windows=args.use_ccs_smart_windows,
         end_after_stage=qi.DebugStage[args.end_after_stage.upper()],
+        stitch_mode=args.stitch_mode,
     )
     if args.shard:
         i, n = args.shard.split("/")

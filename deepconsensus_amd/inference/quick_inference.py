@@ -35,6 +35,7 @@ from deepconsensus_amd.models import config as cfg
 from deepconsensus_amd.models.model import get_model
 from deepconsensus_amd.models.runner import InferenceRunner
 from deepconsensus_amd.postprocess import stitch as stitch_utils
+from deepconsensus_amd.postprocess import stitch_device
 from deepconsensus_amd.preprocess import feeder as pre_feeder
 from deepconsensus_amd.preprocess.windows import DcConfig
 from deepconsensus_amd.utils import constants, phred
@@ -97,6 +98,26 @@ class InferenceOptions:
     # Stop the pipeline early for debugging/runtime testing
     # (quick_inference.py:501,559,715).
     end_after_stage: DebugStage = DebugStage.FULL
+    # Stitcher: "serial" | "pool" | "device". None reads DC_STITCH_MODE
+    # (default "serial"). "device" gap-compacts the model output on the
+    # GPU (postprocess/stitch_device.py) instead of building one
+    # DCModelOutput per window.
+    stitch_mode: Optional[str] = None
+
+
+STITCH_MODES = ("serial", "pool", "device")
+
+
+def resolve_stitch_mode(options: InferenceOptions) -> str:
+    """options.stitch_mode if set, else the DC_STITCH_MODE env knob."""
+    if options.stitch_mode is None:
+        return os.environ.get("DC_STITCH_MODE", "serial")
+    if options.stitch_mode not in STITCH_MODES:
+        raise ValueError(
+            f"stitch_mode must be one of {STITCH_MODES}, got "
+            f"{options.stitch_mode!r}"
+        )
+    return options.stitch_mode
 
 
 @dataclasses.dataclass
@@ -224,6 +245,51 @@ def process_skipped_window(
     )
 
 
+def _gap_tripwire(runner, rows_t, bases_np, gap_frac, n_chunk):
+    """Audits a majority-gap chunk against the fp32 torch path.
+
+    ``bases_np`` is the chunk's host base ids, or a callable returning
+    them: a caller that keeps the chunk on the device then copies it back
+    for suspect chunks only.
+    """
+    # Corruption tripwire: a healthy model rarely predicts majority
+    # gap. A batch-size-dependent native-path regression produced
+    # silent all-gap output (profiles/r01_perf_journal.md "GAP
+    # REGRESSION") — surface it instead of writing garbage FASTQ.
+    if gap_frac > 0.6 and n_chunk > 1 and getattr(
+        runner, "native", False
+    ):
+        if callable(bases_np):
+            bases_np = bases_np()
+        # Corruption tripwire turned hard gate (ADVICE r1): audit a
+        # sample of the suspect batch against the fp32 torch path
+        # and refuse to write FASTQ from a disagreeing native pass.
+        sample = min(32, n_chunk)
+        with torch.no_grad():
+            probs = runner.model(
+                rows_t[:sample].to(runner.device).float(),
+                training=False,
+            )
+        torch_bases = probs.argmax(-1).cpu().numpy()
+        agree = float((bases_np[:sample] == torch_bases).mean())
+        if agree < 0.99:
+            raise RuntimeError(
+                f"native inference path disagrees with the torch "
+                f"reference on {100 * (1 - agree):.1f}% of base "
+                f"calls in a {100 * gap_frac:.0f}%-gap batch of "
+                f"{n_chunk} windows — refusing to write "
+                f"corrupted FASTQ. This indicates a native-kernel "
+                f"regression; re-run with DC_FUSED_FFN=0/"
+                f"smaller --batch_size and file a bug."
+            )
+        log.info(
+            "high gap fraction %.0f%% over %d windows, but the "
+            "native path agrees with the torch reference "
+            "(%.4f) — input is legitimately gappy",
+            100.0 * gap_frac, n_chunk, agree,
+        )
+
+
 _SEQ_LUT = np.frombuffer(constants.SEQ_VOCAB.encode("ascii"), np.uint8)
 
 
@@ -292,41 +358,10 @@ def run_model_on_zmws(
         else:
             bases_t, quals_t = runner.forward_windows(rows_t)
         bases_np = bases_t.cpu().numpy()
-        # Corruption tripwire: a healthy model rarely predicts majority
-        # gap. A batch-size-dependent native-path regression produced
-        # silent all-gap output (profiles/r01_perf_journal.md "GAP
-        # REGRESSION") — surface it instead of writing garbage FASTQ.
-        gap_frac = float((bases_np == 0).mean())
-        if gap_frac > 0.6 and len(chunk) > 1 and getattr(
-            runner, "native", False
-        ):
-            # Corruption tripwire turned hard gate: audit a
-            # sample of the suspect batch against the fp32 torch path
-            # and refuse to write FASTQ from a disagreeing native pass.
-            sample = min(32, len(chunk))
-            with torch.no_grad():
-                probs = runner.model(
-                    rows_t[:sample].to(runner.device).float(),
-                    training=False,
-                )
-            torch_bases = probs.argmax(-1).cpu().numpy()
-            agree = float((bases_np[:sample] == torch_bases).mean())
-            if agree < 0.99:
-                raise RuntimeError(
-                    f"native inference path disagrees with the torch "
-                    f"reference on {100 * (1 - agree):.1f}% of base "
-                    f"calls in a {100 * gap_frac:.0f}%-gap batch of "
-                    f"{len(chunk)} windows — refusing to write "
-                    f"corrupted FASTQ. This indicates a native-kernel "
-                    f"regression; re-run with DC_FUSED_FFN=0/"
-                    f"smaller --batch_size and file a bug."
-                )
-            log.info(
-                "high gap fraction %.0f%% over %d windows, but the "
-                "native path agrees with the torch reference "
-                "(%.4f) — input is legitimately gappy",
-                100.0 * gap_frac, len(chunk), agree,
-            )
+        _gap_tripwire(
+            runner, rows_t, bases_np, float((bases_np == 0).mean()),
+            len(chunk),
+        )
         seq_mat = _SEQ_LUT[bases_np.astype(np.int64)]
         qual_mat = (quals_t.cpu().numpy() + 33).astype(np.uint8)
         for j in range(len(chunk)):
@@ -344,6 +379,156 @@ def run_model_on_zmws(
                 )
             )
     return predictions
+
+
+@dataclasses.dataclass
+class StitchedBatch:
+    """Output of run_model_and_stitch_on_zmws: the stitch plan plus the
+    gap-free bytes of every read of the ZMW batch, on the host."""
+
+    plan: stitch_device.StitchPlan
+    seq_out: np.ndarray  # uint8 ASCII bases, reads back to back
+    qual_out: np.ndarray  # uint8 Phred+33
+    out_off: np.ndarray  # [S + 1] int32 segment offsets into the above
+    n_model: int
+    n_skipped: int
+
+    def __len__(self) -> int:
+        return self.n_model + self.n_skipped
+
+
+def run_model_and_stitch_on_zmws(
+    zmws: List[ZmwWindows],
+    runner: InferenceRunner,
+    options: InferenceOptions,
+) -> StitchedBatch:
+    """Batched model execution with the stitch done on the device.
+
+    Same model loop as run_model_on_zmws, but each chunk's base ids and
+    QVs are copied device-to-device into one flat accumulation buffer per
+    ZMW batch; after the last chunk the stitch_compact kernel drops the
+    gap positions and one D2H copy returns the finished read bytes. No
+    per-window objects are built and gap bytes never leave the device.
+    On a non-native runner the same plan runs on host buffers with the
+    kernel's numpy twin.
+    """
+    stitch_device.check_max_base_quality(options.max_base_quality)
+    pos_list: List[np.ndarray] = []
+    rows_list: List[np.ndarray] = []
+    for z in zmws:
+        if z.rows is not None and len(z.rows):
+            rows_list.append(z.rows)
+            pos_list.append(z.window_pos)
+    n_skipped = sum(len(z.skipped) for z in zmws)
+    if rows_list:
+        all_rows = np.concatenate(rows_list)
+        all_pos = np.concatenate(pos_list)
+        row_length = all_rows.shape[2]
+    else:
+        all_rows = np.empty((0, 0, options.max_length), np.int16)
+        all_pos = np.empty(0, np.int64)
+        row_length = options.max_length
+    n_model = len(all_rows)
+    plan = stitch_device.build_plan(
+        zmws, all_pos, options.max_length, row_length=row_length
+    )
+    n_model_bytes = n_model * row_length
+    n_total = plan.n_source_bytes
+
+    native = bool(getattr(runner, "native", False))
+    # One [2, n_total] buffer: row 0 base ids, row 1 QVs; model windows
+    # first, passthrough windows behind them.
+    if native:
+        acc = torch.empty((2, n_total), dtype=torch.uint8,
+                          device=runner.device)
+    else:
+        all_rows = all_rows.astype(np.float32)
+        acc_np = np.empty((2, n_total), np.uint8)
+    pinned: Dict[Tuple[int, ...], torch.Tensor] = {}
+    use_graph = native and os.environ.get("DC_SERVE_GRAPH", "1") != "0"
+    for i in range(0, n_model, options.batch_size):
+        chunk = np.ascontiguousarray(all_rows[i : i + options.batch_size])
+        n_valid = len(chunk)
+        rows_t = torch.from_numpy(chunk)
+        if native:
+            # Fixed-shape pinned staging, as in run_model_on_zmws. The
+            # per-chunk gap count below synchronises, so the buffer is
+            # free again before the next chunk overwrites it.
+            shape = (
+                (options.batch_size,) + rows_t.shape[1:]
+                if use_graph
+                else tuple(rows_t.shape)
+            )
+            buf = pinned.get(shape)
+            if buf is None:
+                buf = torch.zeros(shape, dtype=rows_t.dtype).pin_memory()
+                pinned[shape] = buf
+            buf[:n_valid].copy_(rows_t)
+            if use_graph and n_valid < shape[0]:
+                buf[n_valid:].zero_()
+            rows_t = buf
+        if use_graph:
+            bases_t, quals_t = runner.forward_windows_graphed(rows_t)
+            bases_t = bases_t[:n_valid]
+            quals_t = quals_t[:n_valid]
+        else:
+            bases_t, quals_t = runner.forward_windows(rows_t)
+        lo, hi = i * row_length, (i + n_valid) * row_length
+        if native:
+            # The graph's output buffer is rewritten by the next replay:
+            # these copies are queued on the same stream ahead of it.
+            acc[0, lo:hi].view(n_valid, row_length).copy_(bases_t)
+            acc[1, lo:hi].view(n_valid, row_length).copy_(quals_t)
+            n_gap = int((bases_t == 0).sum().item())
+            bases_host = lambda b=bases_t: b.cpu().numpy()  # noqa: E731
+        else:
+            bases_host = bases_t.cpu().numpy()
+            acc_np[0, lo:hi] = bases_host.reshape(-1)
+            acc_np[1, lo:hi] = quals_t.cpu().numpy().reshape(-1)
+            n_gap = int((bases_host == 0).sum())
+        # Exact count / size: the same float64 as the host-side mean.
+        _gap_tripwire(
+            runner, rows_t, bases_host, n_gap / (n_valid * row_length),
+            n_valid,
+        )
+
+    n_seg = len(plan.seg_off)
+    if n_seg == 0:
+        seq_out = qual_out = np.empty(0, np.uint8)
+        out_off = np.zeros(1, np.int32)
+    elif native:
+        if n_total > n_model_bytes:
+            extra = torch.from_numpy(
+                np.stack([plan.extra_bases, plan.extra_quals])
+            )
+            acc[:, n_model_bytes:].copy_(extra)
+        segs = torch.from_numpy(
+            np.stack([plan.seg_off, plan.seg_len])
+        ).to(runner.device)
+        seq_t, qual_t, _, off_t = runner.ext.stitch_compact(
+            acc[0], acc[1], segs[0], segs[1]
+        )
+        # One D2H copy: [out_off bytes | seq_out | qual_out].
+        packed = torch.cat(
+            [off_t.view(torch.uint8), seq_t, qual_t]
+        ).cpu().numpy()
+        n_off = 4 * (n_seg + 1)
+        out_off = packed[:n_off].view(np.int32)
+        n_kept = int(out_off[-1])
+        seq_out = packed[n_off : n_off + n_kept]
+        qual_out = packed[n_off + n_kept :]
+    else:
+        acc_np[0, n_model_bytes:] = plan.extra_bases
+        acc_np[1, n_model_bytes:] = plan.extra_quals
+        seq_out, qual_out, _, out_off = (
+            stitch_device.compact_segments_numpy(
+                acc_np[0], acc_np[1], plan.seg_off, plan.seg_len
+            )
+        )
+    return StitchedBatch(
+        plan=plan, seq_out=seq_out, qual_out=qual_out, out_off=out_off,
+        n_model=n_model, n_skipped=n_skipped,
+    )
 
 
 class Timelog:
@@ -450,6 +635,50 @@ def _write_outputs(
             bam_out.write(record)
 
 
+def _write_stitched(
+    stitched: StitchedBatch,
+    output_writer,
+    bam_out,
+    options: InferenceOptions,
+    outcome_counter: stitch_utils.OutcomeCounter,
+):
+    """_write_outputs for a device-stitched batch: filters and writes the
+    already gap-free reads (same FASTQ text, same BAM tags)."""
+    from deepconsensus_amd.dcio import bam as bam_lib
+
+    for name, seq, qual, (ec, np_num_passes, rq, rg) in (
+        stitch_device.finish_reads(
+            stitched.plan, stitched.seq_out, stitched.qual_out,
+            stitched.out_off, options, outcome_counter,
+        )
+    ):
+        seq = seq.decode("ascii")
+        if bam_out is None:
+            output_writer.write(
+                stitch_utils.format_as_fastq(name, seq, qual.decode("ascii"))
+            )
+        else:
+            record = bam_lib.BamRead(
+                qname=name,
+                flag=4,
+                ref_id=-1,
+                pos=-1,
+                mapq=255,
+                seq=seq,
+                query_qualities=(
+                    np.frombuffer(qual, np.uint8).astype(np.int64) - 33
+                ).tolist(),
+                tags={
+                    "ec": ec if ec is not None else -1.0,
+                    "np": np_num_passes or 0,
+                    "rq": rq if rq is not None else -1.0,
+                    "RG": rg or "",
+                    "zm": int(name.split("/")[1]),
+                },
+            )
+            bam_out.write(record)
+
+
 def run(
     subreads_to_ccs: str,
     ccs_bam: str,
@@ -464,6 +693,8 @@ def run(
     """Performs an inference run (quick_inference.py:794-963)."""
     t_start = time.time()
     options = options or InferenceOptions()
+    if resolve_stitch_mode(options) == "device":
+        stitch_device.check_max_base_quality(options.max_base_quality)
 
     # Load params + model. checkpoint == 'random' builds a random-init model
     # (testing only); otherwise a directory with params.json + weights.
@@ -580,7 +811,11 @@ def run(
             len(z.rows) for z in outputs if z.rows is not None
         )
         n_skipped = sum(len(z.skipped) for z in outputs)
-        preds = run_model_on_zmws(outputs, runner, options)
+        stitch_mode = resolve_stitch_mode(options)
+        if stitch_mode == "device":
+            preds = run_model_and_stitch_on_zmws(outputs, runner, options)
+        else:
+            preds = run_model_on_zmws(outputs, runner, options)
         # Per-batch model/skip split (quick_inference.py:688-705).
         total = max(len(preds), 1)
         log.info(
@@ -599,8 +834,12 @@ def run(
         # (plus ~2 s stitch-pool spin-up on the first batch) — the
         # overlap does not pay at this scale; serial is the default
         # and DC_STITCH_MODE=pool keeps the experiment reachable.
-        stitch_mode = os.environ.get("DC_STITCH_MODE", "serial")
-        if (stitch_mode == "pool" and stitch_pool is not None
+        if stitch_mode == "device":
+            _write_stitched(preds, output_writer, bam_out, options,
+                            outcome_counter)
+            timelog.add("stitch_and_write_fastq", batch_name, before,
+                        n_examples, n_subreads, len(inputs))
+        elif (stitch_mode == "pool" and stitch_pool is not None
                 and bam_out is None):
             # Stitch in the PROCESS pool (no GIL contention with the
             # prefetch threads), write the returned text on the ordered

@@ -30,6 +30,7 @@ _SRCS = [
     os.path.join(_OPS_DIR, "hip", "fused_condense.hip"),
     os.path.join(_OPS_DIR, "hip", "ffn_train.hip"),
     os.path.join(_OPS_DIR, "hip", "resid_dropout.hip"),
+    os.path.join(_OPS_DIR, "hip", "stitch_compact.hip"),
 ]
 EXT_NAME = "dc_hip_kernels"
 

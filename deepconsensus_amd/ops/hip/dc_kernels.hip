@@ -240,8 +240,22 @@ at::Tensor resid_drop_fwd(at::Tensor x, at::Tensor y, double alpha,
 std::vector<at::Tensor> resid_drop_bwd(at::Tensor dout, at::Tensor y,
                                        double alpha, double p_drop,
                                        int64_t seed);
+// Defined in stitch_compact.hip.
+std::vector<at::Tensor> stitch_compact(at::Tensor bases, at::Tensor quals,
+                                       at::Tensor seg_off,
+                                       at::Tensor seg_len);
+int64_t stitch_compact_into(at::Tensor bases, at::Tensor quals,
+                            at::Tensor seg_off, at::Tensor seg_len,
+                            at::Tensor seq_out, at::Tensor qual_out,
+                            at::Tensor seg_kept, at::Tensor out_off);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("stitch_compact", &stitch_compact,
+        "Device window stitching: segmented gap compaction -> (seq_out, "
+        "qual_out, seg_kept, out_off)");
+  m.def("stitch_compact_into", &stitch_compact_into,
+        "stitch_compact into caller-owned output buffers; returns "
+        "out_off[S]");
   m.def("fused_condense", &fused_condense,
         "Condenser GEMM [M,560]x[560,N] + fused position-encoding add "
         "(K3+K4)");
