@@ -81,6 +81,13 @@ def _run_main(argv: List[str]) -> None:
                     "pool (process pool, FASTQ only) or device (gap "
                     "compaction on the GPU; numpy on CPU). Default: the "
                     "DC_STITCH_MODE environment variable, else serial")
+    ap.add_argument("--featurize_mode", default=None,
+                    choices=list(qi.FEATURIZE_MODES),
+                    help="window featurizer: host (workers build the "
+                    "int16 model input) or device (workers ship compact "
+                    "per-ZMW planes, the GPU expands them; numpy on CPU). "
+                    "Default: the DC_FEATURIZE_MODE environment variable, "
+                    "else host")
     ap.add_argument("--use_only_gpu_index", type=int, default=None,
                     help="pin inference to this GPU index "
                     "(shorthand for --device cuda:N)")
@@ -107,6 +114,7 @@ def _run_main(argv: List[str]) -> None:
         use_ccs_smart_windows=args.use_ccs_smart_windows,
         end_after_stage=qi.DebugStage[args.end_after_stage.upper()],
         stitch_mode=args.stitch_mode,
+        featurize_mode=args.featurize_mode,
     )
     if args.shard:
         i, n = args.shard.split("/")

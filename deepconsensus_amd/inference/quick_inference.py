@@ -36,6 +36,7 @@ from deepconsensus_amd.models.model import get_model
 from deepconsensus_amd.models.runner import InferenceRunner
 from deepconsensus_amd.postprocess import stitch as stitch_utils
 from deepconsensus_amd.postprocess import stitch_device
+from deepconsensus_amd.preprocess import featurize_device
 from deepconsensus_amd.preprocess import feeder as pre_feeder
 from deepconsensus_amd.preprocess.windows import DcConfig
 from deepconsensus_amd.utils import constants, phred
@@ -103,9 +104,16 @@ class InferenceOptions:
     # GPU (postprocess/stitch_device.py) instead of building one
     # DCModelOutput per window.
     stitch_mode: Optional[str] = None
+    # Featurizer: "host" | "device". None reads DC_FEATURIZE_MODE (default
+    # "host"). "device" has the workers ship compact per-ZMW planes and
+    # expands them into the model input on the GPU
+    # (preprocess/featurize_device.py) instead of building one int16
+    # matrix per window in the worker.
+    featurize_mode: Optional[str] = None
 
 
 STITCH_MODES = ("serial", "pool", "device")
+FEATURIZE_MODES = ("host", "device")
 
 
 def resolve_stitch_mode(options: InferenceOptions) -> str:
@@ -118,6 +126,18 @@ def resolve_stitch_mode(options: InferenceOptions) -> str:
             f"{options.stitch_mode!r}"
         )
     return options.stitch_mode
+
+
+def resolve_featurize_mode(options: InferenceOptions) -> str:
+    """options.featurize_mode if set, else the DC_FEATURIZE_MODE env knob."""
+    mode = options.featurize_mode
+    if mode is None:
+        mode = os.environ.get("DC_FEATURIZE_MODE", "host")
+    if mode not in FEATURIZE_MODES:
+        raise ValueError(
+            f"featurize_mode must be one of {FEATURIZE_MODES}, got {mode!r}"
+        )
+    return mode
 
 
 @dataclasses.dataclass
@@ -142,13 +162,17 @@ class ZmwWindows:
     np_num_passes: Optional[int] = None
     rq: Optional[float] = None
     rg: Optional[str] = None
+    # featurize_mode "device": the model-bound windows as compact planes
+    # plus a window table; ``rows`` is then None.
+    planes: Optional[featurize_device.ZmwPlanes] = None
+
+    @property
+    def n_model(self) -> int:
+        return featurize_device.n_model_windows(self)
 
     @property
     def n_examples(self) -> int:
-        n = len(self.skipped)
-        if self.rows is not None:
-            n += len(self.rows)
-        return n
+        return len(self.skipped) + self.n_model
 
 
 def preprocess_one_zmw(one_zmw) -> ZmwWindows:
@@ -184,23 +208,50 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
     model_rows: List[np.ndarray] = []
     window_pos: List[int] = []
     skipped: List[stitch_utils.DCModelOutput] = []
-    for f in dc_whole.iter_feature_dicts(
-        pw_max=255, ip_max=255, sn_max=500,  # config.py:89-92 defaults
-        out_dtype=np.int16,
-    ):
-        skip = bool(f["overflow"])
-        if not skip and options.skip_windows_above:
-            avg_q = phred.avg_phred(f["ccs_base_quality_scores"])
-            skip = avg_q > options.skip_windows_above
-        if skip:
-            skipped.append(process_skipped_window(f, options))
-            continue
-        model_rows.append(f["subreads"][:, :, 0])
-        window_pos.append(int(f["window_pos"]))
+    ccs = dc_whole.ccs
+    planes = None
+    if resolve_featurize_mode(options) == "device":
+        # None for a ZMW off the fast path: it keeps the host rows.
+        planes = featurize_device.build_planes(dc_whole)
+    if planes is not None:
+        # Same windows, counters and triage as below; a model-bound
+        # window is two table entries instead of an [R, L] matrix.
+        win_start: List[int] = []
+        win_w: List[int] = []
+        for spec in dc_whole.iter_window_specs():
+            if _skip_window(spec.overflow, spec.bq, options):
+                ccs_ids = np.zeros(spec.width, np.uint8)
+                ccs_ids[: spec.w] = planes.ccs[
+                    spec.start : spec.start + spec.w
+                ]
+                skipped.append(_passthrough_output(
+                    ccs_ids, spec.bq, spec.window_pos, dc_whole.name,
+                    ccs.ec, ccs.np_num_passes, ccs.rq, ccs.rg, options,
+                ))
+                continue
+            win_start.append(spec.start)
+            win_w.append(spec.w)
+            window_pos.append(spec.window_pos)
+        planes.win_start = np.asarray(win_start, np.int32)
+        planes.win_w = np.asarray(win_w, np.int32)
+        if not win_start:
+            planes = None
+    else:
+        for f in dc_whole.iter_feature_dicts(
+            pw_max=featurize_device.PW_MAX, ip_max=featurize_device.IP_MAX,
+            sn_max=featurize_device.SN_MAX,  # config.py:89-92 defaults
+            out_dtype=np.int16,
+        ):
+            if _skip_window(
+                f["overflow"], f["ccs_base_quality_scores"], options
+            ):
+                skipped.append(process_skipped_window(f, options))
+                continue
+            model_rows.append(f["subreads"][:, :, 0])
+            window_pos.append(int(f["window_pos"]))
     counter = dc_whole.counter
     if expand_counter:
         counter.update(expand_counter)
-    ccs = dc_whole.ccs
     return ZmwWindows(
         name=zmw,
         window_pos=np.asarray(window_pos, np.int64),
@@ -208,7 +259,17 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
         skipped=skipped,
         counter=counter,
         ec=ccs.ec, np_num_passes=ccs.np_num_passes, rq=ccs.rq, rg=ccs.rg,
+        planes=planes,
     )
+
+
+def _skip_window(overflow, ccs_bq, options: InferenceOptions) -> bool:
+    """Skip triage: overflow windows and windows whose average CCS
+    quality exceeds --skip_windows_above take the CCS passthrough."""
+    skip = bool(overflow)
+    if not skip and options.skip_windows_above:
+        skip = phred.avg_phred(ccs_bq) > options.skip_windows_above
+    return skip
 
 
 def process_skipped_window(
@@ -219,11 +280,25 @@ def process_skipped_window(
     (_, _, _, _, ccs_index, _, _) = cfg.get_indices(
         options.max_passes, options.use_ccs_bq
     )
-    ccs = rows[ccs_index[0], :, 0]
-    ccs_seq = phred.encoded_sequence_to_string(ccs)
-    ccs_quality_scores = np.asarray(
-        feature_dict["ccs_base_quality_scores"], dtype=np.float64
+    return _passthrough_output(
+        rows[ccs_index[0], :, 0],
+        feature_dict["ccs_base_quality_scores"],
+        feature_dict["window_pos"],
+        feature_dict["name"],
+        feature_dict["ec"], feature_dict["np_num_passes"],
+        feature_dict["rq"], feature_dict["rg"],
+        options,
     )
+
+
+def _passthrough_output(
+    ccs_ids: np.ndarray, ccs_bq, window_pos, name, ec, np_num_passes, rq,
+    rg, options: InferenceOptions,
+) -> stitch_utils.DCModelOutput:
+    """The passthrough DCModelOutput from the window's padded CCS base
+    ids and padded CCS qualities alone."""
+    ccs_seq = phred.encoded_sequence_to_string(ccs_ids)
+    ccs_quality_scores = np.asarray(ccs_bq, dtype=np.float64)
     if options.ccs_calibration_values.enabled:
         ccs_quality_scores = calibration_lib.calibrate_quality_scores(
             ccs_quality_scores, options.ccs_calibration_values
@@ -234,14 +309,14 @@ def process_skipped_window(
     ccs_quality_scores = np.maximum(ccs_quality_scores, 0)
     ccs_quality_scores = ccs_quality_scores.astype(np.int32)
     return stitch_utils.DCModelOutput(
-        window_pos=feature_dict["window_pos"],
-        molecule_name=feature_dict["name"],
+        window_pos=window_pos,
+        molecule_name=name,
         sequence=ccs_seq,
         quality_string=phred.quality_scores_to_string(ccs_quality_scores),
-        ec=feature_dict["ec"],
-        np_num_passes=feature_dict["np_num_passes"],
-        rq=feature_dict["rq"],
-        rg=feature_dict["rg"],
+        ec=ec,
+        np_num_passes=np_num_passes,
+        rq=rq,
+        rg=rg,
     )
 
 
@@ -293,6 +368,151 @@ def _gap_tripwire(runner, rows_t, bases_np, gap_frac, n_chunk):
 _SEQ_LUT = np.frombuffer(constants.SEQ_VOCAB.encode("ascii"), np.uint8)
 
 
+class _ModelChunks:
+    """The model input of one ZMW batch, produced batch_size windows at a
+    time; the chunk loop of run_model_on_zmws and
+    run_model_and_stitch_on_zmws.
+
+    Host rows (featurize_mode "host"): the pre-stacked per-ZMW matrices
+    are concatenated once and each chunk is staged through a pinned
+    buffer. Planes (featurize_mode "device"): the batch's planes and
+    tables cross to the device in one copy and each chunk is expanded
+    there by the window_featurize kernel; ZMWs that kept host rows have
+    theirs copied into their slots. On a non-native runner the kernel's
+    numpy twin expands the chunk on the host.
+    """
+
+    def __init__(self, zmws: List[ZmwWindows], runner: InferenceRunner,
+                 options: InferenceOptions):
+        self.runner = runner
+        self.batch_size = options.batch_size
+        self.model_zmws = [
+            z for z in zmws if featurize_device.n_model_windows(z)
+        ]
+        self.all_pos = (
+            np.concatenate([z.window_pos for z in self.model_zmws])
+            if self.model_zmws else np.empty(0, np.int64)
+        )
+        # Native path: features are non-negative and <= SN_MAX (500)
+        # after clipping, and the embed kernel casts to int anyway, so
+        # int16 staging halves H2D traffic with bit-identical results
+        # (numpy's truncation toward zero == the kernel's (int)v == the
+        # torch model's .long()).
+        self.native = bool(getattr(runner, "native", False))
+        self.use_graph = (
+            self.native and os.environ.get("DC_SERVE_GRAPH", "1") != "0"
+        )
+        self.batch: Optional[featurize_device.FeaturizeBatch] = None
+        if any(getattr(z, "planes", None) is not None
+               for z in self.model_zmws):
+            self._init_planes()
+        elif self.model_zmws:
+            all_rows = np.concatenate([z.rows for z in self.model_zmws])
+            self.row_length = all_rows.shape[2]
+            if not self.native:
+                all_rows = all_rows.astype(np.float32)
+            self.all_rows = all_rows
+            self.n_model = len(all_rows)
+            self.pinned: Dict[Tuple[int, ...], torch.Tensor] = {}
+        else:
+            self.row_length = options.max_length
+            self.n_model = 0
+
+    def _init_planes(self) -> None:
+        if not self.native:
+            self.batch = featurize_device.pack_batch(self.model_zmws)
+        else:
+            device = self.runner.device
+            staging: List[torch.Tensor] = []
+
+            def alloc(nbytes: int) -> np.ndarray:
+                staging.append(
+                    torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+                )
+                return staging[0].numpy()
+
+            # With the graph every chunk is batch_size table entries:
+            # the tail is padded with -1 (zero) windows once, here.
+            self.batch = batch = featurize_device.pack_batch(
+                self.model_zmws,
+                pad_multiple=self.batch_size if self.use_graph else 1,
+                alloc=alloc,
+            )
+            blob = staging[0].to(device, non_blocking=True)
+
+            def view(name: str, array: np.ndarray) -> torch.Tensor:
+                lo = batch.offsets[name]
+                flat = blob[lo : lo + array.nbytes]
+                return flat.view(getattr(torch, array.dtype.name))
+
+            self.dev = (
+                view("sub", batch.sub), view("ccs", batch.ccs),
+                view("ccs_bq", batch.ccs_bq),
+                view("zmw_tab", batch.zmw_tab).view(batch.zmw_tab.shape),
+            )
+            self.win_tab = view("win_tab", batch.win_tab).view(
+                batch.win_tab.shape
+            )
+            if batch.fallback_rows is not None:
+                self.fallback_rows = torch.from_numpy(
+                    batch.fallback_rows
+                ).to(device)
+                self.fallback_idx = torch.from_numpy(
+                    batch.fallback_idx
+                ).to(device)
+        self.n_model = self.batch.n_windows
+        self.row_length = self.batch.max_length
+
+    def chunk(self, i: int) -> Tuple[torch.Tensor, int]:
+        """(rows_t, n_valid) for windows [i, i + batch_size): the model
+        input (padded to batch_size when the graph is in use) and the
+        number of real windows in it."""
+        if self.batch is not None:
+            return self._chunk_from_planes(i)
+        chunk = np.ascontiguousarray(self.all_rows[i : i + self.batch_size])
+        n_valid = len(chunk)
+        rows_t = torch.from_numpy(chunk)
+        if self.native:
+            # Fixed-shape pinned buffer: partial tails are zero-padded
+            # so the hipGraph-captured step replays at one shape (pad
+            # windows cost compute on the final chunk only; their
+            # outputs are sliced away).
+            shape = (
+                (self.batch_size,) + rows_t.shape[1:]
+                if self.use_graph
+                else tuple(rows_t.shape)
+            )
+            buf = self.pinned.get(shape)
+            if buf is None:
+                buf = torch.zeros(shape, dtype=rows_t.dtype).pin_memory()
+                self.pinned[shape] = buf
+            buf[:n_valid].copy_(rows_t)
+            if self.use_graph and n_valid < shape[0]:
+                buf[n_valid:].zero_()
+            rows_t = buf
+        return rows_t, n_valid
+
+    def _chunk_from_planes(self, i: int) -> Tuple[torch.Tensor, int]:
+        batch = self.batch
+        n_valid = min(self.batch_size, self.n_model - i)
+        if not self.native:
+            rows = featurize_device.featurize_chunk_numpy(
+                batch, i, i + n_valid
+            )
+            return torch.from_numpy(rows.astype(np.float32)), n_valid
+        hi = i + (self.batch_size if self.use_graph else n_valid)
+        rows_t = self.runner.ext.window_featurize(
+            *self.dev, self.win_tab[i:hi], batch.n_rows, batch.max_length,
+            batch.max_passes, batch.use_ccs_bq,
+        )
+        k0, k1 = batch.fallback_range(i, i + n_valid)
+        if k1 > k0:
+            rows_t.index_copy_(
+                0, self.fallback_idx[k0:k1] - i, self.fallback_rows[k0:k1]
+            )
+        return rows_t, n_valid
+
+
 def run_model_on_zmws(
     zmws: List[ZmwWindows],
     runner: InferenceRunner,
@@ -306,51 +526,19 @@ def run_model_on_zmws(
     (one LUT pass + one +33 pass per chunk).
     """
     predictions: List[stitch_utils.DCModelOutput] = []
-    # Per-window owner metadata, in concatenation order.
-    owners: List[ZmwWindows] = []
-    pos_list: List[np.ndarray] = []
-    rows_list: List[np.ndarray] = []
     for z in zmws:
         predictions.extend(z.skipped)
-        if z.rows is not None and len(z.rows):
-            rows_list.append(z.rows)
-            pos_list.append(z.window_pos)
-            owners.extend([z] * len(z.rows))
-    if not rows_list:
+    chunks = _ModelChunks(zmws, runner, options)
+    if not chunks.n_model:
         return predictions
-    all_rows = np.concatenate(rows_list)
-    all_pos = np.concatenate(pos_list)
-    # Native path: features are non-negative and <= SN_MAX (500) after
-    # clipping, and the embed kernel casts to int anyway, so int16 staging
-    # halves H2D traffic with bit-identical results (numpy's truncation
-    # toward zero == the kernel's (int)v == the torch model's .long()).
-    use_i16 = bool(getattr(runner, "native", False))
-    if not use_i16:
-        all_rows = all_rows.astype(np.float32)
-    pinned: Dict[Tuple[int, ...], torch.Tensor] = {}
-    use_graph = use_i16 and os.environ.get("DC_SERVE_GRAPH", "1") != "0"
-    for i in range(0, len(all_rows), options.batch_size):
-        chunk = np.ascontiguousarray(all_rows[i : i + options.batch_size])
-        n_valid = len(chunk)
-        rows_t = torch.from_numpy(chunk)
-        if use_i16:
-            # Fixed-shape pinned buffer: partial tails are zero-padded
-            # so the hipGraph-captured step replays at one shape (pad
-            # windows cost compute on the final chunk only; their
-            # outputs are sliced away).
-            shape = (
-                (options.batch_size,) + rows_t.shape[1:]
-                if use_graph
-                else tuple(rows_t.shape)
-            )
-            buf = pinned.get(shape)
-            if buf is None:
-                buf = torch.zeros(shape, dtype=rows_t.dtype).pin_memory()
-                pinned[shape] = buf
-            buf[:n_valid].copy_(rows_t)
-            if use_graph and n_valid < shape[0]:
-                buf[n_valid:].zero_()
-            rows_t = buf
+    # Per-window owner metadata, in concatenation order.
+    owners: List[ZmwWindows] = []
+    for z in chunks.model_zmws:
+        owners.extend([z] * featurize_device.n_model_windows(z))
+    all_pos = chunks.all_pos
+    use_graph = chunks.use_graph
+    for i in range(0, chunks.n_model, options.batch_size):
+        rows_t, n_valid = chunks.chunk(i)
         if use_graph:
             bases_t, quals_t = runner.forward_windows_graphed(rows_t)
             bases_t = bases_t[:n_valid]
@@ -360,11 +548,11 @@ def run_model_on_zmws(
         bases_np = bases_t.cpu().numpy()
         _gap_tripwire(
             runner, rows_t, bases_np, float((bases_np == 0).mean()),
-            len(chunk),
+            n_valid,
         )
         seq_mat = _SEQ_LUT[bases_np.astype(np.int64)]
         qual_mat = (quals_t.cpu().numpy() + 33).astype(np.uint8)
-        for j in range(len(chunk)):
+        for j in range(n_valid):
             z = owners[i + j]
             predictions.append(
                 stitch_utils.DCModelOutput(
@@ -413,22 +601,11 @@ def run_model_and_stitch_on_zmws(
     kernel's numpy twin.
     """
     stitch_device.check_max_base_quality(options.max_base_quality)
-    pos_list: List[np.ndarray] = []
-    rows_list: List[np.ndarray] = []
-    for z in zmws:
-        if z.rows is not None and len(z.rows):
-            rows_list.append(z.rows)
-            pos_list.append(z.window_pos)
     n_skipped = sum(len(z.skipped) for z in zmws)
-    if rows_list:
-        all_rows = np.concatenate(rows_list)
-        all_pos = np.concatenate(pos_list)
-        row_length = all_rows.shape[2]
-    else:
-        all_rows = np.empty((0, 0, options.max_length), np.int16)
-        all_pos = np.empty(0, np.int64)
-        row_length = options.max_length
-    n_model = len(all_rows)
+    chunks = _ModelChunks(zmws, runner, options)
+    all_pos = chunks.all_pos
+    row_length = chunks.row_length
+    n_model = chunks.n_model
     plan = stitch_device.build_plan(
         zmws, all_pos, options.max_length, row_length=row_length
     )
@@ -442,31 +619,12 @@ def run_model_and_stitch_on_zmws(
         acc = torch.empty((2, n_total), dtype=torch.uint8,
                           device=runner.device)
     else:
-        all_rows = all_rows.astype(np.float32)
         acc_np = np.empty((2, n_total), np.uint8)
-    pinned: Dict[Tuple[int, ...], torch.Tensor] = {}
-    use_graph = native and os.environ.get("DC_SERVE_GRAPH", "1") != "0"
+    use_graph = chunks.use_graph
     for i in range(0, n_model, options.batch_size):
-        chunk = np.ascontiguousarray(all_rows[i : i + options.batch_size])
-        n_valid = len(chunk)
-        rows_t = torch.from_numpy(chunk)
-        if native:
-            # Fixed-shape pinned staging, as in run_model_on_zmws. The
-            # per-chunk gap count below synchronises, so the buffer is
-            # free again before the next chunk overwrites it.
-            shape = (
-                (options.batch_size,) + rows_t.shape[1:]
-                if use_graph
-                else tuple(rows_t.shape)
-            )
-            buf = pinned.get(shape)
-            if buf is None:
-                buf = torch.zeros(shape, dtype=rows_t.dtype).pin_memory()
-                pinned[shape] = buf
-            buf[:n_valid].copy_(rows_t)
-            if use_graph and n_valid < shape[0]:
-                buf[n_valid:].zero_()
-            rows_t = buf
+        # The per-chunk gap count below synchronises, so the staging
+        # buffer is free again before the next chunk overwrites it.
+        rows_t, n_valid = chunks.chunk(i)
         if use_graph:
             bases_t, quals_t = runner.forward_windows_graphed(rows_t)
             bases_t = bases_t[:n_valid]
@@ -693,6 +851,7 @@ def run(
     """Performs an inference run (quick_inference.py:794-963)."""
     t_start = time.time()
     options = options or InferenceOptions()
+    resolve_featurize_mode(options)  # a bad value fails here, not in a worker
     if resolve_stitch_mode(options) == "device":
         stitch_device.check_max_base_quality(options.max_base_quality)
 
@@ -807,9 +966,7 @@ def run(
             return
 
         before = time.time()
-        n_model = sum(
-            len(z.rows) for z in outputs if z.rows is not None
-        )
+        n_model = sum(z.n_model for z in outputs)
         n_skipped = sum(len(z.skipped) for z in outputs)
         stitch_mode = resolve_stitch_mode(options)
         if stitch_mode == "device":

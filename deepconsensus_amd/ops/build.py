@@ -31,6 +31,7 @@ _SRCS = [
     os.path.join(_OPS_DIR, "hip", "ffn_train.hip"),
     os.path.join(_OPS_DIR, "hip", "resid_dropout.hip"),
     os.path.join(_OPS_DIR, "hip", "stitch_compact.hip"),
+    os.path.join(_OPS_DIR, "hip", "window_featurize.hip"),
 ]
 EXT_NAME = "dc_hip_kernels"
 

@@ -248,8 +248,22 @@ int64_t stitch_compact_into(at::Tensor bases, at::Tensor quals,
                             at::Tensor seg_off, at::Tensor seg_len,
                             at::Tensor seq_out, at::Tensor qual_out,
                             at::Tensor seg_kept, at::Tensor out_off);
+// Defined in window_featurize.hip.
+at::Tensor window_featurize(at::Tensor sub, at::Tensor ccs,
+                            at::Tensor ccs_bq, at::Tensor zmw_tab,
+                            at::Tensor win_tab, int64_t R, int64_t L,
+                            int64_t max_passes, bool use_ccs_bq);
+void window_featurize_into(at::Tensor sub, at::Tensor ccs,
+                           at::Tensor ccs_bq, at::Tensor zmw_tab,
+                           at::Tensor win_tab, at::Tensor out,
+                           int64_t max_passes, bool use_ccs_bq);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("window_featurize", &window_featurize,
+        "Device window featurization: compact ZMW planes + window table "
+        "-> int16 [N, R, L] model input");
+  m.def("window_featurize_into", &window_featurize_into,
+        "window_featurize into a caller-owned int16 [N, R, L] tensor");
   m.def("stitch_compact", &stitch_compact,
         "Device window stitching: segmented gap compaction -> (seq_out, "
         "qual_out, seg_kept, out_off)");

@@ -25,6 +25,7 @@ from typing import Any, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from deepconsensus_amd.postprocess import stitch as stitch_utils
+from deepconsensus_amd.preprocess.featurize_device import n_model_windows
 from deepconsensus_amd.utils import constants, phred
 
 # Largest QV whose +33 byte is still printable ASCII ('~').
@@ -161,7 +162,8 @@ def build_plan(
     """Builds the segment table for one ZMW batch.
 
     ``zmws`` are ZmwWindows-like objects (``name``, ``window_pos``,
-    ``rows``, ``skipped``, ``ec``, ``np_num_passes``, ``rq``, ``rg``).
+    ``rows`` or ``planes``, ``skipped``, ``ec``, ``np_num_passes``, ``rq``,
+    ``rg``).
     Model windows are numbered in concatenation order (ZMW by ZMW, the
     order ``run_model_on_zmws`` stacks them); ``all_pos`` is their
     concatenated ``window_pos`` (derived from ``zmws`` when None).
@@ -186,9 +188,9 @@ def build_plan(
         return i
 
     skipped = [sk for z in zmws for sk in z.skipped]
-    model_zmws = [z for z in zmws if z.rows is not None and len(z.rows)]
+    model_zmws = [z for z in zmws if n_model_windows(z)]
     model_counts = np.fromiter(
-        (len(z.rows) for z in model_zmws), np.int64, len(model_zmws)
+        (n_model_windows(z) for z in model_zmws), np.int64, len(model_zmws)
     )
     n_model = int(model_counts.sum())
     if all_pos is None:

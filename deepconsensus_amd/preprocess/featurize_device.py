@@ -1,0 +1,412 @@
+"""Device-side window featurization: compact planes on the host, the
+``int16 [B, R, L]`` model input expanded on the device.
+
+The host featurizer (windows.py: iter_feature_dicts) expands every window
+into an 85 x 100 int16 matrix in the worker; the matrix is then pickled,
+concatenated, staged and copied to the device. Nearly all of it is
+redundant: column slices of per-ZMW planes the worker already holds, one
+strand value per row, four SN values, and zero padding. This module ships
+the planes instead:
+
+* ``build_planes``  — worker, per ZMW: the ``uint8`` planes of the spaced
+  ZMW (``ZmwPlanes``), or None when the ZMW needs the per-window path.
+* ``pack_batch``    — main thread, per ZMW batch: planes back to back in
+  one buffer, a per-ZMW table and a per-window table (``FeaturizeBatch``),
+  validated on the host.
+* expansion         — ``ops/hip/window_featurize.hip`` on the device, or
+  its numpy twin ``featurize_windows_numpy`` (CPU backend and test oracle).
+
+Window enumeration, counters and the skip triage stay in windows.py /
+quick_inference.py and are shared with the host path.
+"""
+from __future__ import annotations
+
+import dataclasses
+from typing import Any, Callable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from deepconsensus_amd.preprocess.windows import DcExample
+from deepconsensus_amd.utils import constants
+
+# format_rows' clipping (models/config.py PW_MAX / IP_MAX / SN_MAX).
+PW_MAX = 255
+IP_MAX = 255
+SN_MAX = 500
+
+# Leading columns of a zmw_tab row; strand[max_passes] and sn[4] follow.
+TAB_SUB_OFF, TAB_CCS_OFF, TAB_BQ_OFF, TAB_N_SUB, TAB_W = range(5)
+TAB_FIXED = 5
+
+
+def tensor_height(max_passes: int, use_ccs_bq: bool) -> int:
+    return 4 * max_passes + 1 + int(bool(use_ccs_bq)) + 4
+
+
+@dataclasses.dataclass
+class ZmwPlanes:
+    """Compact model input of one ZMW: ``n_sub = min(n_subreads,
+    max_passes)`` subreads over the spaced width W."""
+
+    sub: np.ndarray  # uint8 [3, n_sub, W]: base ids, pw, ip
+    strand: np.ndarray  # uint8 [n_sub]
+    sn: np.ndarray  # int16 [4], clipped to 0..SN_MAX
+    ccs: np.ndarray  # uint8 [W] CCS base ids
+    ccs_bq: Optional[np.ndarray]  # int16 [W], only with use_ccs_bq
+    win_start: np.ndarray  # int32 [n_model], model-bound windows only
+    win_w: np.ndarray  # int32 [n_model]
+    max_passes: int
+    max_length: int
+
+    @property
+    def n_sub(self) -> int:
+        return self.sub.shape[1]
+
+    @property
+    def width(self) -> int:
+        return self.ccs.shape[0]
+
+
+def _encode_bases(bases: np.ndarray) -> np.ndarray:
+    enc = np.zeros(bases.shape, np.uint8)
+    for k, base in enumerate(constants.SEQ_VOCAB):
+        if k:
+            enc[bases == base] = k
+    return enc
+
+
+def build_planes(dc: DcExample) -> Optional[ZmwPlanes]:
+    """Planes of a spaced ZMW, with an empty window table.
+
+    Returns None when the ZMW does not meet the fast-path precondition
+    (training ZMW, irregular read widths, pw/ip not already ``uint8``,
+    qualities not spaced to W): the caller then featurizes that ZMW on
+    the host. Values equal what iter_feature_dicts(pw_max=255,
+    ip_max=255, sn_max=500, out_dtype=int16) puts into its matrices.
+    """
+    if not dc.is_evenly_spaced_inference:
+        return None
+    config = dc.config
+    subs = dc.subreads[: config.max_passes]
+    n, W = len(subs), dc.width
+    if any(r.pw.dtype != np.uint8 or r.ip.dtype != np.uint8 for r in subs):
+        return None
+    sub = np.zeros((3, n, W), np.uint8)
+    sn = np.zeros(4, np.int16)
+    if n:
+        sub[0] = _encode_bases(np.stack([r.bases for r in subs]))
+        # uint8 is 0..255 already; the clip documents format_rows' bound.
+        np.clip(np.stack([r.pw for r in subs]), 0, PW_MAX, out=sub[1])
+        np.clip(np.stack([r.ip for r in subs]), 0, IP_MAX, out=sub[2])
+        sn_raw = np.asarray(subs[0].sn)
+        if sn_raw.shape != (4,):
+            return None
+        sn = np.clip(sn_raw, 0, SN_MAX).astype(np.int16)
+    ccs_bq = None
+    if config.use_ccs_bq:
+        bq = np.asarray(dc.ccs.base_quality_scores)
+        if bq.shape != (W,):
+            return None
+        ccs_bq = bq.astype(np.int16)
+    return ZmwPlanes(
+        sub=sub,
+        strand=np.array([int(r.strand) for r in subs], np.uint8),
+        sn=sn,
+        ccs=_encode_bases(dc.ccs.bases),
+        ccs_bq=ccs_bq,
+        win_start=np.empty(0, np.int32),
+        win_w=np.empty(0, np.int32),
+        max_passes=config.max_passes,
+        max_length=config.max_length,
+    )
+
+
+def n_model_windows(z: Any) -> int:
+    """Model-bound windows of a ZmwWindows-like object, whichever form
+    (``rows`` or ``planes``) it carries them in."""
+    if z.rows is not None:
+        return len(z.rows)
+    if getattr(z, "planes", None) is not None:
+        return len(z.planes.win_start)
+    return 0
+
+
+@dataclasses.dataclass
+class FeaturizeBatch:
+    """Planes and tables of one ZMW batch.
+
+    ``blob`` is one ``uint8`` buffer; ``zmw_tab``, ``win_tab``, ``ccs_bq``,
+    ``sub`` and ``ccs`` are views into it at ``offsets[name]`` (bytes), so
+    one copy moves everything to the device.
+
+    zmw_tab int64 [Z, 5 + max_passes + 4]: element offsets of the ZMW's
+    planes in ``sub`` / ``ccs`` / ``ccs_bq``, n_sub, W, strand[max_passes],
+    sn[4]. A ZMW's ``sub`` block is its [3, n_sub, W] array, row-major.
+
+    win_tab int32 [n_padded, 3]: (zmw_index, start, w) per model window,
+    in concatenation order. zmw_index -1 means the kernel writes zeros:
+    tail padding, or a window of a fallback ZMW whose host ``rows`` the
+    caller copies in (``fallback_idx`` / ``fallback_rows``).
+    """
+
+    blob: np.ndarray
+    offsets: dict
+    zmw_tab: np.ndarray
+    win_tab: np.ndarray
+    ccs_bq: np.ndarray  # int16, empty without use_ccs_bq
+    sub: np.ndarray
+    ccs: np.ndarray
+    n_windows: int  # without the tail padding
+    n_rows: int
+    max_length: int
+    max_passes: int
+    use_ccs_bq: bool
+    fallback_idx: np.ndarray  # int64, ascending window indices
+    fallback_rows: Optional[np.ndarray]  # int16 [len(fallback_idx), R, L]
+
+    def fallback_range(self, lo: int, hi: int) -> Tuple[int, int]:
+        """Slice of fallback_idx / fallback_rows inside windows [lo, hi)."""
+        k0, k1 = np.searchsorted(self.fallback_idx, [lo, hi])
+        return int(k0), int(k1)
+
+
+def _check(cond: bool, message: str) -> None:
+    if not cond:
+        raise ValueError(f"pack_batch: {message}")
+
+
+def pack_batch(
+    zmws: Sequence[Any],
+    pad_multiple: int = 1,
+    alloc: Optional[Callable[[int], np.ndarray]] = None,
+) -> FeaturizeBatch:
+    """Packs the model windows of a ZMW batch for the featurize kernel.
+
+    ``zmws`` are ZmwWindows-like objects carrying either ``planes`` or
+    host ``rows``; window order is ZMW order. ``pad_multiple`` pads the
+    window table with -1 entries to a multiple of it (fixed-shape graph
+    replays). ``alloc(nbytes)`` returns the ``uint8`` buffer to pack
+    into (pinned memory, say); numpy allocates otherwise.
+
+    Raises ValueError when a table entry would make the kernel read
+    outside a plane or when the ZMWs disagree on the layout.
+    """
+    _check(pad_multiple >= 1, "pad_multiple must be positive")
+    plane_zmws: List[ZmwPlanes] = []
+    win_parts: List[np.ndarray] = []
+    fb_idx: List[np.ndarray] = []
+    fb_rows: List[np.ndarray] = []
+    n_windows = 0
+    layout = None  # (max_passes, max_length, use_ccs_bq)
+    rows_shape = None
+    for z in zmws:
+        n = n_model_windows(z)
+        if not n:
+            continue
+        if z.rows is not None:
+            rows = np.asarray(z.rows)
+            _check(rows.ndim == 3 and rows.dtype == np.int16,
+                   "fallback rows must be int16 [n, R, L]")
+            _check(rows_shape in (None, rows.shape[1:]),
+                   "fallback rows of different shapes")
+            rows_shape = rows.shape[1:]
+            fb_idx.append(np.arange(n_windows, n_windows + n))
+            fb_rows.append(rows)
+            win_parts.append(np.full((n, 3), -1, np.int32))
+            win_parts[-1][:, 1:] = 0
+        else:
+            p = z.planes
+            this = (int(p.max_passes), int(p.max_length),
+                    p.ccs_bq is not None)
+            _check(layout in (None, this),
+                   f"ZMWs disagree on (max_passes, max_length, "
+                   f"use_ccs_bq): {layout} and {this}")
+            layout = this
+            n_sub, W = p.n_sub, p.width
+            _check(p.sub.dtype == np.uint8 and p.sub.shape == (3, n_sub, W),
+                   "sub must be uint8 [3, n_sub, W]")
+            _check(p.ccs.dtype == np.uint8, "ccs must be uint8")
+            _check(n_sub <= p.max_passes,
+                   f"n_sub={n_sub} exceeds max_passes={p.max_passes}")
+            _check(p.strand.shape == (n_sub,), "strand must be [n_sub]")
+            _check(np.shape(p.sn) == (4,), "sn must be [4]")
+            if p.ccs_bq is not None:
+                _check(p.ccs_bq.dtype == np.int16
+                       and p.ccs_bq.shape == (W,),
+                       "ccs_bq must be int16 [W]")
+            start = np.asarray(p.win_start, np.int64)
+            w = np.asarray(p.win_w, np.int64)
+            _check(start.shape == w.shape == (n,),
+                   "win_start and win_w must be [n_model]")
+            _check(bool((start >= 0).all()), "window with start < 0")
+            _check(bool(((w >= 1) & (w <= p.max_length)).all()),
+                   f"window width outside 1..{p.max_length}")
+            _check(bool((start + w <= W).all()),
+                   f"window ends past the ZMW width {W}")
+            tab = np.empty((n, 3), np.int32)
+            tab[:, 0] = len(plane_zmws)
+            tab[:, 1] = start
+            tab[:, 2] = w
+            win_parts.append(tab)
+            plane_zmws.append(p)
+        n_windows += n
+
+    if layout is None:
+        _check(rows_shape is not None or n_windows == 0, "no layout")
+        if rows_shape is not None:
+            R, L = rows_shape
+            use_ccs_bq = (R - 5) % 4 != 0
+            layout = ((R - 5 - int(use_ccs_bq)) // 4, L, use_ccs_bq)
+        else:
+            layout = (0, 0, False)
+    max_passes, max_length, use_ccs_bq = layout
+    n_rows = tensor_height(max_passes, use_ccs_bq)
+    if rows_shape is not None:
+        _check(tuple(rows_shape) == (n_rows, max_length),
+               f"fallback rows are {tuple(rows_shape)}, planes expand to "
+               f"{(n_rows, max_length)}")
+
+    n_zmw = len(plane_zmws)
+    n_padded = -(-n_windows // pad_multiple) * pad_multiple
+    n_col = TAB_FIXED + max_passes + 4
+    sizes = [
+        ("zmw_tab", np.int64, n_zmw * n_col),
+        ("win_tab", np.int32, n_padded * 3),
+        ("ccs_bq", np.int16,
+         sum(p.width for p in plane_zmws) if use_ccs_bq else 0),
+        ("sub", np.uint8, sum(p.sub.size for p in plane_zmws)),
+        ("ccs", np.uint8, sum(p.width for p in plane_zmws)),
+    ]
+    # Descending item size, so every view is aligned to its own type.
+    offsets, total = {}, 0
+    for name, dtype, count in sizes:
+        offsets[name] = total
+        total += count * np.dtype(dtype).itemsize
+    blob = np.empty(total, np.uint8) if alloc is None else alloc(total)
+    _check(isinstance(blob, np.ndarray) and blob.dtype == np.uint8
+           and blob.shape == (total,) and blob.flags.c_contiguous,
+           "alloc must return a contiguous uint8 array of nbytes")
+    views = {}
+    for name, dtype, count in sizes:
+        lo = offsets[name]
+        views[name] = blob[lo : lo + count * np.dtype(dtype).itemsize].view(
+            dtype
+        )
+    zmw_tab = views["zmw_tab"].reshape(n_zmw, n_col)
+    win_tab = views["win_tab"].reshape(n_padded, 3)
+    zmw_tab[:] = 0
+    sub_off = ccs_off = 0
+    for i, p in enumerate(plane_zmws):
+        n_sub, W = p.n_sub, p.width
+        zmw_tab[i, TAB_SUB_OFF] = sub_off
+        zmw_tab[i, TAB_CCS_OFF] = ccs_off
+        zmw_tab[i, TAB_BQ_OFF] = ccs_off if use_ccs_bq else 0
+        zmw_tab[i, TAB_N_SUB] = n_sub
+        zmw_tab[i, TAB_W] = W
+        zmw_tab[i, TAB_FIXED : TAB_FIXED + n_sub] = p.strand
+        zmw_tab[i, TAB_FIXED + max_passes :] = p.sn
+        views["sub"][sub_off : sub_off + p.sub.size] = p.sub.reshape(-1)
+        views["ccs"][ccs_off : ccs_off + W] = p.ccs
+        if use_ccs_bq:
+            views["ccs_bq"][ccs_off : ccs_off + W] = p.ccs_bq
+        sub_off += p.sub.size
+        ccs_off += W
+    # Offsets inside the arrays: true by construction, checked anyway.
+    _check(sub_off == views["sub"].size and ccs_off == views["ccs"].size,
+           "plane offsets do not add up to the packed arrays")
+    if n_windows:
+        win_tab[:n_windows] = np.concatenate(win_parts)
+    win_tab[n_windows:, 0] = -1
+    win_tab[n_windows:, 1:] = 0
+    return FeaturizeBatch(
+        blob=blob, offsets=offsets, zmw_tab=zmw_tab, win_tab=win_tab,
+        ccs_bq=views["ccs_bq"], sub=views["sub"], ccs=views["ccs"],
+        n_windows=n_windows, n_rows=n_rows, max_length=max_length,
+        max_passes=max_passes, use_ccs_bq=use_ccs_bq,
+        fallback_idx=(np.concatenate(fb_idx) if fb_idx
+                      else np.empty(0, np.int64)),
+        fallback_rows=np.concatenate(fb_rows) if fb_rows else None,
+    )
+
+
+def featurize_windows_numpy(
+    batch: FeaturizeBatch,
+    lo: int,
+    hi: int,
+    R: int,
+    L: int,
+    max_passes: int,
+    use_ccs_bq: bool,
+) -> np.ndarray:
+    """Numpy twin of the ``window_featurize`` kernel: windows [lo, hi) of
+    ``batch.win_tab`` as ``int16 [hi - lo, R, L]``.
+
+    Like the kernel it never trusts the tables: a window whose zmw_index
+    is outside the ZMW table, or whose ZMW's planes do not lie inside the
+    packed arrays, comes out as zeros; n_sub is clamped to max_passes,
+    start to [0, W] and w to [0, min(L, W - start)]. Fallback windows
+    (zmw_index -1) are zeros here; the caller copies their rows in.
+    """
+    if R != tensor_height(max_passes, use_ccs_bq):
+        raise ValueError(
+            f"R={R} does not match max_passes={max_passes}, "
+            f"use_ccs_bq={use_ccs_bq}"
+        )
+    zmw_tab, win_tab = batch.zmw_tab, batch.win_tab
+    if zmw_tab.ndim != 2 or zmw_tab.shape[1] != TAB_FIXED + max_passes + 4:
+        raise ValueError("zmw_tab does not have 5 + max_passes + 4 columns")
+    if not 0 <= lo <= hi <= len(win_tab):
+        raise ValueError("window range outside win_tab")
+    sub, ccs, bq_all = batch.sub, batch.ccs, batch.ccs_bq
+    mp = max_passes
+    out = np.zeros((hi - lo, R, L), np.int16)
+    for j in range(hi - lo):
+        zi, start, w = (int(v) for v in win_tab[lo + j])
+        if not 0 <= zi < len(zmw_tab):
+            continue
+        row = zmw_tab[zi]
+        sub_off, ccs_off, bq_off, n_raw, W = (
+            int(v) for v in row[:TAB_FIXED]
+        )
+        if (
+            n_raw < 0 or W < 0 or sub_off < 0 or ccs_off < 0
+            or sub_off + 3 * n_raw * W > len(sub)
+            or ccs_off + W > len(ccs)
+            or (use_ccs_bq and (bq_off < 0 or bq_off + W > len(bq_all)))
+        ):
+            continue
+        n_sub = min(n_raw, mp)
+        start = min(max(start, 0), W)
+        w = min(max(w, 0), L, W - start)
+        x = out[j]
+        if n_sub:
+            planes = sub[sub_off : sub_off + 3 * n_raw * W].reshape(
+                3, n_raw, W
+            )
+            for f in range(3):
+                x[f * mp : f * mp + n_sub, :w] = planes[
+                    f, :n_sub, start : start + w
+                ]
+            x[3 * mp : 3 * mp + n_sub] = row[
+                TAB_FIXED : TAB_FIXED + n_sub, None
+            ]
+            x[R - 4 :] = row[TAB_FIXED + mp :, None]
+        x[4 * mp, :w] = ccs[ccs_off + start : ccs_off + start + w]
+        if use_ccs_bq:
+            x[4 * mp + 1, :w] = bq_all[bq_off + start : bq_off + start + w]
+            x[4 * mp + 1, w:] = -1
+    return out
+
+
+def featurize_chunk_numpy(
+    batch: FeaturizeBatch, lo: int, hi: int
+) -> np.ndarray:
+    """CPU backend: the twin plus the host rows of fallback ZMWs."""
+    out = featurize_windows_numpy(
+        batch, lo, hi, batch.n_rows, batch.max_length, batch.max_passes,
+        batch.use_ccs_bq,
+    )
+    k0, k1 = batch.fallback_range(lo, hi)
+    if k1 > k0:
+        out[batch.fallback_idx[k0:k1] - lo] = batch.fallback_rows[k0:k1]
+    return out

@@ -94,6 +94,20 @@ class DcConfig:
 
 
 @dataclasses.dataclass
+class WindowSpec:
+    """One inference window as columns [start, start + w) of the spaced
+    ZMW. ``width`` is the padded width (max_length, or more for an
+    overflow window); ``bq`` the CCS qualities padded to it with -1."""
+
+    start: int
+    w: int
+    width: int
+    overflow: bool
+    window_pos: int
+    bq: np.ndarray
+
+
+@dataclasses.dataclass
 class DcExample:
     """Container generating model inputs from spaced reads."""
 
@@ -241,6 +255,61 @@ class DcExample:
                 self.name, reads, self.config, _overflow=self._overflow
             )
 
+    def iter_window_specs(self):
+        """Enumerates the inference windows of an evenly spaced ZMW.
+
+        The column bookkeeping of the vectorized featurizers, shared by
+        iter_feature_dicts (host matrices) and the compact-plane path
+        (preprocess/featurize_device.py): same windows, same counters,
+        same padded CCS qualities either way. Resets and fills
+        ``self.counter``; windows without any CCS index are counted and
+        not yielded.
+        """
+        max_length = self.config.max_length
+        W = self.width
+        ccs_bq_all = np.asarray(self.ccs.base_quality_scores)
+        ccs_idx_all = self.ccs.ccs_idx
+        self.counter = collections.Counter()
+        start_pos = 0
+        for window_width in self.calculate_windows(max_length):
+            self.counter[f"example_width_bucket_{window_width}"] += 1
+            if start_pos > self.ccs_width:
+                break
+            s, e = start_pos, min(start_pos + window_width, W)
+            start_pos += window_width
+            w_idx = ccs_idx_all[s:e]
+            valid = w_idx >= 0
+            if not valid.any():
+                self.counter["n_examples_no_ccs_idx"] += 1
+                continue
+            overflow = window_width > max_length
+            if overflow:
+                self.counter["n_examples_overflow"] += 1
+                # Read.pad still applies: an overflow window clipped at
+                # the ZMW end shorter than max_length pads back up to it.
+                width = max(e - s, max_length)
+            else:
+                self.counter["n_examples_skip_large_windows_keep"] += 1
+                width = max_length
+            w = e - s
+            bq = ccs_bq_all[s:e]
+            if w < width:  # Read.pad pads quality scores with -1
+                bq_full = np.full(width, -1, ccs_bq_all.dtype)
+                bq_full[:w] = bq
+                bq = bq_full
+            yield WindowSpec(
+                start=s, w=w, width=width, overflow=overflow,
+                window_pos=int(w_idx[valid].min()), bq=bq,
+            )
+
+    @property
+    def is_evenly_spaced_inference(self) -> bool:
+        """Precondition of the vectorized featurizers: no label, and
+        every read as wide as the CCS."""
+        return not self.is_training and all(
+            len(r.bases) == self.width for r in self.reads
+        )
+
     def iter_feature_dicts(self, pw_max=None, ip_max=None, sn_max=None,
                            out_dtype=None):
         """Vectorized inference twin of
@@ -265,9 +334,7 @@ class DcExample:
         fmt = (pw_max is not None or ip_max is not None
                or sn_max is not None or out_dtype is not None)
         dtype = out_dtype or constants.NP_DATA_TYPE
-        if self.is_training or any(
-            len(r.bases) != self.width for r in self.reads
-        ):
+        if not self.is_evenly_spaced_inference:
             from deepconsensus_amd.models import data as data_lib
             from deepconsensus_amd.models.config import Params
 
@@ -286,7 +353,6 @@ class DcExample:
                 yield f
             return
         config = self.config
-        max_length = config.max_length
         subs = self.subreads[: config.max_passes]
         n = len(subs)
         ccs = self.ccs
@@ -314,8 +380,6 @@ class DcExample:
         for k, base in enumerate(constants.SEQ_VOCAB):
             if k:
                 ccs_enc[ccs.bases == base] = k
-        ccs_bq_all = np.asarray(ccs.base_quality_scores)
-        ccs_idx_all = ccs.ccs_idx
         n_rows = config.tensor_height
         scalars = dict(
             name=self.name,
@@ -324,29 +388,10 @@ class DcExample:
         )
         keep = self.keep_subreads
 
-        self.counter = collections.Counter()
-        start_pos = 0
-        for window_width in self.calculate_windows(max_length):
-            self.counter[f"example_width_bucket_{window_width}"] += 1
-            if start_pos > self.ccs_width:
-                break
-            s, e = start_pos, min(start_pos + window_width, W)
-            start_pos += window_width
-            w_idx = ccs_idx_all[s:e]
-            valid = w_idx >= 0
-            if not valid.any():
-                self.counter["n_examples_no_ccs_idx"] += 1
-                continue
-            overflow = window_width > max_length
-            if overflow:
-                self.counter["n_examples_overflow"] += 1
-                # Read.pad still applies: an overflow window clipped at
-                # the ZMW end shorter than max_length pads back up to it.
-                width = max(e - s, max_length)
-            else:
-                self.counter["n_examples_skip_large_windows_keep"] += 1
-                width = max_length
-            w = e - s
+        for spec in self.iter_window_specs():
+            s, w, width = spec.start, spec.w, spec.width
+            e = s + w
+            overflow, bq = spec.overflow, spec.bq
             data = np.zeros((n_rows, width), dtype)
             if n:
                 data[config.indices("bases", n), :w] = sub_enc[:, s:e]
@@ -355,18 +400,13 @@ class DcExample:
                 data[config.indices("strand", n)] = strand_col
                 data[config.indices("sn")] = sn_col
             data[config.indices("ccs"), :w] = ccs_enc[s:e]
-            bq = ccs_bq_all[s:e]
-            if w < width:  # Read.pad pads quality scores with -1
-                bq_full = np.full(width, -1, ccs_bq_all.dtype)
-                bq_full[:w] = bq
-                bq = bq_full
             if config.use_ccs_bq:
                 data[config.indices("ccs_bq"), :w] = bq[:w]
                 data[config.indices("ccs_bq"), w:] = -1
             out = {
                 "subreads": data[:, :, None],
                 "subreads/num_passes": keep,
-                "window_pos": int(w_idx[valid].min()),
+                "window_pos": spec.window_pos,
                 "ccs_base_quality_scores": bq,
                 "overflow": overflow,
                 **scalars,
