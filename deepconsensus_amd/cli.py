@@ -88,6 +88,15 @@ def _run_main(argv: List[str]) -> None:
                     "per-ZMW planes, the GPU expands them; numpy on CPU). "
                     "Default: the DC_FEATURIZE_MODE environment variable, "
                     "else host")
+    ap.add_argument("--passthrough_mode", default=None,
+                    choices=list(qi.PASSTHROUGH_MODES),
+                    help="CCS passthrough of skipped windows: host (workers "
+                    "build one output object per skipped window) or device "
+                    "(workers ship one table entry per skipped window, the "
+                    "GPU fills the stitch buffer from the CCS planes; numpy "
+                    "on CPU). device needs --featurize_mode device and "
+                    "--stitch_mode device. Default: the DC_PASSTHROUGH_MODE "
+                    "environment variable, else host")
     ap.add_argument("--use_only_gpu_index", type=int, default=None,
                     help="pin inference to this GPU index "
                     "(shorthand for --device cuda:N)")
@@ -115,6 +124,7 @@ def _run_main(argv: List[str]) -> None:
         end_after_stage=qi.DebugStage[args.end_after_stage.upper()],
         stitch_mode=args.stitch_mode,
         featurize_mode=args.featurize_mode,
+        passthrough_mode=args.passthrough_mode,
     )
     if args.shard:
         i, n = args.shard.split("/")

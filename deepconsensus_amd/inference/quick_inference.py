@@ -110,10 +110,17 @@ class InferenceOptions:
     # (preprocess/featurize_device.py) instead of building one int16
     # matrix per window in the worker.
     featurize_mode: Optional[str] = None
+    # CCS passthrough of skipped windows: "host" | "device". None reads
+    # DC_PASSTHROUGH_MODE (default "host"). "device" has the workers ship
+    # one passthrough table entry per skipped window instead of one
+    # DCModelOutput, and fills the stitch buffer from the CCS planes on
+    # the GPU. Only defined with featurize_mode and stitch_mode "device".
+    passthrough_mode: Optional[str] = None
 
 
 STITCH_MODES = ("serial", "pool", "device")
 FEATURIZE_MODES = ("host", "device")
+PASSTHROUGH_MODES = ("host", "device")
 
 
 def resolve_stitch_mode(options: InferenceOptions) -> str:
@@ -140,6 +147,29 @@ def resolve_featurize_mode(options: InferenceOptions) -> str:
     return mode
 
 
+def resolve_passthrough_mode(options: InferenceOptions) -> str:
+    """options.passthrough_mode if set, else the DC_PASSTHROUGH_MODE env
+    knob. "device" needs featurize mode and stitch mode "device"."""
+    mode = options.passthrough_mode
+    if mode is None:
+        mode = os.environ.get("DC_PASSTHROUGH_MODE", "host")
+    if mode not in PASSTHROUGH_MODES:
+        raise ValueError(
+            f"passthrough_mode must be one of {PASSTHROUGH_MODES}, got "
+            f"{mode!r}"
+        )
+    if mode == "device":
+        others = (resolve_featurize_mode(options),
+                  resolve_stitch_mode(options))
+        if others != ("device", "device"):
+            raise ValueError(
+                f"passthrough_mode 'device' needs featurize_mode 'device' "
+                f"and stitch_mode 'device', got featurize_mode "
+                f"{others[0]!r} and stitch_mode {others[1]!r}"
+            )
+    return mode
+
+
 @dataclasses.dataclass
 class ZmwWindows:
     """Worker output for one ZMW: model windows pre-stacked, skipped
@@ -163,7 +193,10 @@ class ZmwWindows:
     rq: Optional[float] = None
     rg: Optional[str] = None
     # featurize_mode "device": the model-bound windows as compact planes
-    # plus a window table; ``rows`` is then None.
+    # plus a window table; ``rows`` is then None. passthrough_mode
+    # "device": the planes also carry the skipped windows as a passthrough
+    # table (``skipped`` is then empty), and stay when no window is
+    # model-bound.
     planes: Optional[featurize_device.ZmwPlanes] = None
 
     @property
@@ -171,8 +204,13 @@ class ZmwWindows:
         return featurize_device.n_model_windows(self)
 
     @property
+    def n_skipped(self) -> int:
+        """Skipped windows, as objects or as passthrough table entries."""
+        return len(self.skipped) + featurize_device.n_table_passthrough(self)
+
+    @property
     def n_examples(self) -> int:
-        return len(self.skipped) + self.n_model
+        return self.n_skipped + self.n_model
 
 
 def preprocess_one_zmw(one_zmw) -> ZmwWindows:
@@ -218,8 +256,23 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
         # window is two table entries instead of an [R, L] matrix.
         win_start: List[int] = []
         win_w: List[int] = []
+        # Device passthrough: a skipped window is a table entry as well,
+        # when the ZMW's CCS qualities fit the uint8 code.
+        pt: List[Tuple[int, int, int, int]] = []
+        if resolve_passthrough_mode(options) == "device":
+            planes.ccs_q = featurize_device.encode_ccs_qualities(
+                ccs.base_quality_scores
+            )
+            if (planes.ccs_q is not None
+                    and planes.ccs_q.shape != planes.ccs.shape):
+                planes.ccs_q = None
         for spec in dc_whole.iter_window_specs():
             if _skip_window(spec.overflow, spec.bq, options):
+                if planes.ccs_q is not None:
+                    pt.append(
+                        (spec.start, spec.w, spec.width, spec.window_pos)
+                    )
+                    continue
                 ccs_ids = np.zeros(spec.width, np.uint8)
                 ccs_ids[: spec.w] = planes.ccs[
                     spec.start : spec.start + spec.w
@@ -234,8 +287,18 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
             window_pos.append(spec.window_pos)
         planes.win_start = np.asarray(win_start, np.int32)
         planes.win_w = np.asarray(win_w, np.int32)
+        if pt:
+            cols = np.asarray(pt, np.int64).T
+            planes.pt_start, planes.pt_w, planes.pt_width = (
+                c.astype(np.int32) for c in cols[:3]
+            )
+            planes.pt_pos = cols[3]
+        else:
+            planes.ccs_q = None  # nothing reads it
         if not win_start:
-            planes = None
+            # Without model windows only the passthrough table needs the
+            # planes, and of them only ccs and ccs_q.
+            planes = planes.without_subreads() if pt else None
     else:
         for f in dc_whole.iter_feature_dicts(
             pw_max=featurize_device.PW_MAX, ip_max=featurize_device.IP_MAX,
@@ -291,13 +354,10 @@ def process_skipped_window(
     )
 
 
-def _passthrough_output(
-    ccs_ids: np.ndarray, ccs_bq, window_pos, name, ec, np_num_passes, rq,
-    rg, options: InferenceOptions,
-) -> stitch_utils.DCModelOutput:
-    """The passthrough DCModelOutput from the window's padded CCS base
-    ids and padded CCS qualities alone."""
-    ccs_seq = phred.encoded_sequence_to_string(ccs_ids)
+def passthrough_qualities(ccs_bq, options: InferenceOptions) -> np.ndarray:
+    """Output QVs (int32) of a passthrough window from its CCS qualities:
+    calibration when enabled, then the clamp to 0..max_base_quality.
+    Elementwise, so it is also what passthrough_quality_lut tabulates."""
     ccs_quality_scores = np.asarray(ccs_bq, dtype=np.float64)
     if options.ccs_calibration_values.enabled:
         ccs_quality_scores = calibration_lib.calibrate_quality_scores(
@@ -307,7 +367,48 @@ def _passthrough_output(
         ccs_quality_scores, options.max_base_quality
     )
     ccs_quality_scores = np.maximum(ccs_quality_scores, 0)
-    ccs_quality_scores = ccs_quality_scores.astype(np.int32)
+    return ccs_quality_scores.astype(np.int32)
+
+
+def passthrough_quality_lut(options: InferenceOptions) -> np.ndarray:
+    """uint8 [256]: ZmwPlanes.ccs_q code (q + 1) -> output QV, by
+    passthrough_qualities itself over q = -1..254. The device passthrough
+    looks QVs up here, so no quality arithmetic runs on the GPU."""
+    stitch_device.check_max_base_quality(options.max_base_quality)
+    return passthrough_qualities(np.arange(-1, 255), options).astype(
+        np.uint8
+    )
+
+
+def _runner_quality_lut(runner, options: InferenceOptions, native: bool):
+    """passthrough_quality_lut, built (and on a native runner uploaded)
+    once per runner and set of quality options instead of per ZMW batch."""
+    c = options.ccs_calibration_values
+    key = (options.max_base_quality, c.enabled, c.threshold, c.w, c.b)
+    cache = getattr(runner, "_passthrough_luts", None)
+    if cache is None:
+        cache = {}
+        try:
+            runner._passthrough_luts = cache
+        except AttributeError:  # a runner that takes no attributes
+            pass
+    lut = cache.get(key)
+    if lut is None:
+        lut = passthrough_quality_lut(options)
+        if native:
+            lut = torch.from_numpy(lut).to(runner.device)
+        cache[key] = lut
+    return lut
+
+
+def _passthrough_output(
+    ccs_ids: np.ndarray, ccs_bq, window_pos, name, ec, np_num_passes, rq,
+    rg, options: InferenceOptions,
+) -> stitch_utils.DCModelOutput:
+    """The passthrough DCModelOutput from the window's padded CCS base
+    ids and padded CCS qualities alone."""
+    ccs_seq = phred.encoded_sequence_to_string(ccs_ids)
+    ccs_quality_scores = passthrough_qualities(ccs_bq, options)
     return stitch_utils.DCModelOutput(
         window_pos=window_pos,
         molecule_name=name,
@@ -403,8 +504,17 @@ class _ModelChunks:
             self.native and os.environ.get("DC_SERVE_GRAPH", "1") != "0"
         )
         self.batch: Optional[featurize_device.FeaturizeBatch] = None
+        # ZMWs with something to pack: model windows, or (passthrough_mode
+        # "device") passthrough table entries. A batch of the latter alone
+        # still crosses to the device: its CCS planes are the source of the
+        # passthrough fill.
+        self.packed_zmws = [
+            z for z in zmws
+            if featurize_device.n_model_windows(z)
+            or featurize_device.n_table_passthrough(z)
+        ]
         if any(getattr(z, "planes", None) is not None
-               for z in self.model_zmws):
+               for z in self.packed_zmws):
             self._init_planes()
         elif self.model_zmws:
             all_rows = np.concatenate([z.rows for z in self.model_zmws])
@@ -420,7 +530,7 @@ class _ModelChunks:
 
     def _init_planes(self) -> None:
         if not self.native:
-            self.batch = featurize_device.pack_batch(self.model_zmws)
+            self.batch = featurize_device.pack_batch(self.packed_zmws)
         else:
             device = self.runner.device
             staging: List[torch.Tensor] = []
@@ -434,7 +544,7 @@ class _ModelChunks:
             # With the graph every chunk is batch_size table entries:
             # the tail is padded with -1 (zero) windows once, here.
             self.batch = batch = featurize_device.pack_batch(
-                self.model_zmws,
+                self.packed_zmws,
                 pad_multiple=self.batch_size if self.use_graph else 1,
                 alloc=alloc,
             )
@@ -452,6 +562,11 @@ class _ModelChunks:
             )
             self.win_tab = view("win_tab", batch.win_tab).view(
                 batch.win_tab.shape
+            )
+            # Inputs of passthrough_fill_into, ahead of the LUT.
+            self.pt_dev = (
+                self.dev[1], view("ccs_q", batch.ccs_q), self.dev[3],
+                view("pt_tab", batch.pt_tab).view(batch.pt_tab.shape),
             )
             if batch.fallback_rows is not None:
                 self.fallback_rows = torch.from_numpy(
@@ -527,6 +642,11 @@ def run_model_on_zmws(
     """
     predictions: List[stitch_utils.DCModelOutput] = []
     for z in zmws:
+        if featurize_device.n_table_passthrough(z):
+            raise ValueError(
+                "passthrough table entries need the device stitcher "
+                "(run_model_and_stitch_on_zmws)"
+            )
         predictions.extend(z.skipped)
     chunks = _ModelChunks(zmws, runner, options)
     if not chunks.n_model:
@@ -601,7 +721,10 @@ def run_model_and_stitch_on_zmws(
     kernel's numpy twin.
     """
     stitch_device.check_max_base_quality(options.max_base_quality)
-    n_skipped = sum(len(z.skipped) for z in zmws)
+    n_skipped = sum(
+        len(z.skipped) + featurize_device.n_table_passthrough(z)
+        for z in zmws
+    )
     chunks = _ModelChunks(zmws, runner, options)
     all_pos = chunks.all_pos
     row_length = chunks.row_length
@@ -610,11 +733,19 @@ def run_model_and_stitch_on_zmws(
         zmws, all_pos, options.max_length, row_length=row_length
     )
     n_model_bytes = n_model * row_length
+    n_table_bytes = plan.n_table_bytes
     n_total = plan.n_source_bytes
+    if n_table_bytes != (chunks.batch.n_pt_bytes if chunks.batch else 0):
+        raise ValueError(
+            "stitch plan and packed passthrough table disagree on the "
+            "size of the passthrough region"
+        )
+    # Object passthrough windows sit behind the table ones.
+    extra_lo = n_model_bytes + n_table_bytes
 
     native = bool(getattr(runner, "native", False))
     # One [2, n_total] buffer: row 0 base ids, row 1 QVs; model windows
-    # first, passthrough windows behind them.
+    # first, passthrough windows behind them (StitchPlan has the order).
     if native:
         acc = torch.empty((2, n_total), dtype=torch.uint8,
                           device=runner.device)
@@ -655,11 +786,19 @@ def run_model_and_stitch_on_zmws(
         seq_out = qual_out = np.empty(0, np.uint8)
         out_off = np.zeros(1, np.int32)
     elif native:
-        if n_total > n_model_bytes:
+        if n_table_bytes:
+            # One launch per ZMW batch, on the stream of the model loop and
+            # of stitch_compact, which reads what it writes.
+            runner.ext.passthrough_fill_into(
+                *chunks.pt_dev, _runner_quality_lut(runner, options, True),
+                acc[0, n_model_bytes:extra_lo],
+                acc[1, n_model_bytes:extra_lo],
+            )
+        if n_total > extra_lo:
             extra = torch.from_numpy(
                 np.stack([plan.extra_bases, plan.extra_quals])
             )
-            acc[:, n_model_bytes:].copy_(extra)
+            acc[:, extra_lo:].copy_(extra)
         segs = torch.from_numpy(
             np.stack([plan.seg_off, plan.seg_len])
         ).to(runner.device)
@@ -676,8 +815,16 @@ def run_model_and_stitch_on_zmws(
         seq_out = packed[n_off : n_off + n_kept]
         qual_out = packed[n_off + n_kept :]
     else:
-        acc_np[0, n_model_bytes:] = plan.extra_bases
-        acc_np[1, n_model_bytes:] = plan.extra_quals
+        if n_table_bytes:
+            batch = chunks.batch
+            featurize_device.passthrough_fill_numpy(
+                batch.ccs, batch.ccs_q, batch.zmw_tab, batch.pt_tab,
+                _runner_quality_lut(runner, options, False),
+                acc_np[0, n_model_bytes:extra_lo],
+                acc_np[1, n_model_bytes:extra_lo],
+            )
+        acc_np[0, extra_lo:] = plan.extra_bases
+        acc_np[1, extra_lo:] = plan.extra_quals
         seq_out, qual_out, _, out_off = (
             stitch_device.compact_segments_numpy(
                 acc_np[0], acc_np[1], plan.seg_off, plan.seg_len
@@ -852,6 +999,7 @@ def run(
     t_start = time.time()
     options = options or InferenceOptions()
     resolve_featurize_mode(options)  # a bad value fails here, not in a worker
+    resolve_passthrough_mode(options)  # so does a mode combination
     if resolve_stitch_mode(options) == "device":
         stitch_device.check_max_base_quality(options.max_base_quality)
 
@@ -967,7 +1115,7 @@ def run(
 
         before = time.time()
         n_model = sum(z.n_model for z in outputs)
-        n_skipped = sum(len(z.skipped) for z in outputs)
+        n_skipped = sum(z.n_skipped for z in outputs)
         stitch_mode = resolve_stitch_mode(options)
         if stitch_mode == "device":
             preds = run_model_and_stitch_on_zmws(outputs, runner, options)

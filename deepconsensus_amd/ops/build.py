@@ -32,6 +32,7 @@ _SRCS = [
     os.path.join(_OPS_DIR, "hip", "resid_dropout.hip"),
     os.path.join(_OPS_DIR, "hip", "stitch_compact.hip"),
     os.path.join(_OPS_DIR, "hip", "window_featurize.hip"),
+    os.path.join(_OPS_DIR, "hip", "passthrough_fill.hip"),
 ]
 EXT_NAME = "dc_hip_kernels"
 

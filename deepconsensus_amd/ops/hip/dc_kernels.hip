@@ -257,8 +257,16 @@ void window_featurize_into(at::Tensor sub, at::Tensor ccs,
                            at::Tensor ccs_bq, at::Tensor zmw_tab,
                            at::Tensor win_tab, at::Tensor out,
                            int64_t max_passes, bool use_ccs_bq);
+// Defined in passthrough_fill.hip.
+void passthrough_fill_into(at::Tensor ccs, at::Tensor ccs_q,
+                           at::Tensor zmw_tab, at::Tensor pt_tab,
+                           at::Tensor qual_lut, at::Tensor bases_out,
+                           at::Tensor quals_out);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("passthrough_fill_into", &passthrough_fill_into,
+        "Device CCS passthrough: skipped windows of the packed planes -> "
+        "caller-owned base-id and QV rows of the stitch buffer");
   m.def("window_featurize", &window_featurize,
         "Device window featurization: compact ZMW planes + window table "
         "-> int16 [N, R, L] model input");

@@ -25,7 +25,10 @@ from typing import Any, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from deepconsensus_amd.postprocess import stitch as stitch_utils
-from deepconsensus_amd.preprocess.featurize_device import n_model_windows
+from deepconsensus_amd.preprocess.featurize_device import (
+    n_model_windows,
+    n_table_passthrough,
+)
 from deepconsensus_amd.utils import constants, phred
 
 # Largest QV whose +33 byte is still printable ASCII ('~').
@@ -105,7 +108,11 @@ class StitchPlan:
 
     The flat source buffers are laid out as ``n_model * row_length`` model
     bytes (window i at ``[i * row_length, (i + 1) * row_length)``) followed
-    by ``extra_bases`` / ``extra_quals`` (the passthrough windows).
+    by the passthrough windows: first the ``n_table_bytes`` of the windows
+    that arrive as passthrough table entries of their ZMW's planes (ZMW
+    order, then window order; filled from the CCS planes by
+    ``passthrough_fill``), then ``extra_bases`` / ``extra_quals``, the
+    windows that arrive as ``DCModelOutput`` objects.
     Read r owns segments ``read_seg_start[r] : read_seg_start[r + 1]``.
     """
 
@@ -115,14 +122,16 @@ class StitchPlan:
     read_metadata: List[ReadMetadata]
     seg_off: np.ndarray  # [S] int32
     seg_len: np.ndarray  # [S] int32
-    extra_bases: np.ndarray  # uint8 ids of the passthrough windows
-    extra_quals: np.ndarray  # uint8 QVs of the passthrough windows
+    extra_bases: np.ndarray  # uint8 ids of the object passthrough windows
+    extra_quals: np.ndarray  # uint8 QVs of the object passthrough windows
     n_model: int
     row_length: int
+    n_table_bytes: int = 0  # region of the table passthrough windows
 
     @property
     def n_source_bytes(self) -> int:
-        return self.n_model * self.row_length + len(self.extra_bases)
+        return (self.n_model * self.row_length + self.n_table_bytes
+                + len(self.extra_bases))
 
 
 def _decode_passthrough(
@@ -175,6 +184,11 @@ def build_plan(
     windows are all empty — is ``empty_sequence`` and contributes no
     segments. A ZMW without any window never reaches the stitcher there
     and is not a read here either.
+
+    A skipped window is either a ``DCModelOutput`` in ``z.skipped`` or an
+    entry of the passthrough table of ``z.planes`` (``pt_pos``,
+    ``pt_width``); both take the same place in the prediction list, and a
+    table entry carries its ZMW's name and tags.
     """
     row_length = max_length if row_length is None else row_length
     names: List[str] = []
@@ -203,15 +217,67 @@ def build_plan(
         raise ValueError("all_pos does not match the model window count")
 
     extra_bases, extra_quals, sk_len = _decode_passthrough(skipped)
-    n_skipped = len(skipped)
-    if n_model * row_length + len(extra_bases) >= 2**31:
+
+    # Skipped windows in prediction-list order: ZMW by ZMW, a ZMW's either
+    # as objects or as passthrough table entries of its planes. Objects
+    # are walked one by one; table entries are whole arrays per ZMW.
+    # s_owner indexes ``skipped`` for an object, ``zmws`` for an entry.
+    s_name: List[np.ndarray] = []
+    s_pos: List[np.ndarray] = []
+    s_tab: List[np.ndarray] = []
+    s_owner: List[np.ndarray] = []
+    tab_len: List[np.ndarray] = []
+    n_objects = 0
+    for zi, z in enumerate(zmws):
+        n_obj, n_tab = len(z.skipped), n_table_passthrough(z)
+        if n_obj:
+            s_name.append(np.fromiter(
+                (intern(sk.molecule_name) for sk in z.skipped), np.int64,
+                n_obj,
+            ))
+            s_pos.append(np.fromiter(
+                (int(sk.window_pos) for sk in z.skipped), np.int64, n_obj
+            ))
+            s_tab.append(np.zeros(n_obj, bool))
+            s_owner.append(np.arange(n_objects, n_objects + n_obj))
+            n_objects += n_obj
+        if n_tab:
+            p = z.planes
+            pos = np.asarray(p.pt_pos, np.int64)
+            width = np.asarray(p.pt_width, np.int64)
+            if pos.shape != (n_tab,) or width.shape != (n_tab,):
+                raise ValueError(
+                    "passthrough table columns of different lengths"
+                )
+            if (width < 0).any():
+                raise ValueError("passthrough window of negative width")
+            s_name.append(np.full(n_tab, intern(z.name), np.int64))
+            s_pos.append(pos)
+            s_tab.append(np.ones(n_tab, bool))
+            s_owner.append(np.full(n_tab, zi, np.int64))
+            tab_len.append(width)
+
+    def cat(parts: List[np.ndarray], dtype) -> np.ndarray:
+        return np.concatenate(parts) if parts else np.empty(0, dtype)
+
+    is_tab = cat(s_tab, bool)
+    skip_owner = cat(s_owner, np.int64)
+    tab_len_all = cat(tab_len, np.int64)
+    n_skipped = len(is_tab)
+    n_table_bytes = int(tab_len_all.sum())
+    table_lo = n_model * row_length
+    if table_lo + n_table_bytes + len(extra_bases) >= 2**31:
         raise ValueError("ZMW batch too large for int32 segment offsets")
+    s_len = np.empty(n_skipped, np.int64)
+    s_len[is_tab] = tab_len_all
+    s_len[~is_tab] = sk_len
+    s_off = np.empty(n_skipped, np.int64)
+    s_off[is_tab] = table_lo + np.cumsum(tab_len_all) - tab_len_all
+    s_off[~is_tab] = table_lo + n_table_bytes + np.cumsum(sk_len) - sk_len
 
     # Per-window columns in prediction-list order: skipped, then model.
     w_name = np.concatenate([
-        np.fromiter(
-            (intern(sk.molecule_name) for sk in skipped), np.int64, n_skipped
-        ),
+        cat(s_name, np.int64),
         np.repeat(
             np.fromiter(
                 (intern(z.name) for z in model_zmws), np.int64,
@@ -220,17 +286,11 @@ def build_plan(
             model_counts,
         ),
     ])
-    w_pos = np.concatenate([
-        np.fromiter(
-            (int(sk.window_pos) for sk in skipped), np.int64, n_skipped
-        ),
-        all_pos,
-    ])
+    w_pos = np.concatenate([cat(s_pos, np.int64), all_pos])
     w_off = np.concatenate([
-        n_model * row_length + np.cumsum(sk_len) - sk_len,
-        np.arange(n_model, dtype=np.int64) * row_length,
+        s_off, np.arange(n_model, dtype=np.int64) * row_length,
     ])
-    w_len = np.concatenate([sk_len, np.full(n_model, row_length, np.int64)])
+    w_len = np.concatenate([s_len, np.full(n_model, row_length, np.int64)])
     n_windows = len(w_name)
 
     # Python string order of the names, as sorted() on the tuples gives.
@@ -268,10 +328,13 @@ def build_plan(
     for w in first:
         read_names.append(sorted_names[w_rank[w]])
         src = int(order[w])
-        o = (
-            skipped[src] if src < n_skipped
-            else model_zmws[model_owner[src - n_skipped]]
-        )
+        if src >= n_skipped:
+            o = model_zmws[model_owner[src - n_skipped]]
+        elif is_tab[src]:
+            # What a skipped object of this ZMW would carry.
+            o = zmws[skip_owner[src]]
+        else:
+            o = skipped[skip_owner[src]]
         read_metadata.append((o.ec, o.np_num_passes, o.rq, o.rg))
 
     return StitchPlan(
@@ -285,6 +348,7 @@ def build_plan(
         extra_quals=extra_quals,
         n_model=n_model,
         row_length=row_length,
+        n_table_bytes=n_table_bytes,
     )
 
 

@@ -18,6 +18,12 @@ the planes instead:
 
 Window enumeration, counters and the skip triage stay in windows.py /
 quick_inference.py and are shared with the host path.
+
+With passthrough_mode "device" the planes also carry the skipped windows:
+a passthrough table (``ZmwPlanes.pt_*``) and the CCS qualities as ``uint8``
+codes (``ccs_q``). ``pack_batch`` turns them into ``pt_tab`` and
+``ops/hip/passthrough_fill.hip`` (numpy twin: ``passthrough_fill_numpy``)
+writes their base ids and QVs into the stitch buffer.
 """
 from __future__ import annotations
 
@@ -57,6 +63,20 @@ class ZmwPlanes:
     win_w: np.ndarray  # int32 [n_model]
     max_passes: int
     max_length: int
+    # Passthrough table (passthrough_mode "device"): one entry per skipped
+    # window, columns [start, start + w) padded to ``width`` (above
+    # max_length for an overflow window). ``ccs_q`` is the CCS quality of
+    # every column coded q + 1 (0 = the -1 padding value); None means the
+    # ZMW keeps host ``skipped`` objects and the table is empty.
+    ccs_q: Optional[np.ndarray] = None  # uint8 [W]
+    pt_start: np.ndarray = dataclasses.field(
+        default_factory=lambda: np.empty(0, np.int32))
+    pt_w: np.ndarray = dataclasses.field(
+        default_factory=lambda: np.empty(0, np.int32))
+    pt_width: np.ndarray = dataclasses.field(
+        default_factory=lambda: np.empty(0, np.int32))
+    pt_pos: np.ndarray = dataclasses.field(  # window_pos per entry
+        default_factory=lambda: np.empty(0, np.int64))
 
     @property
     def n_sub(self) -> int:
@@ -65,6 +85,28 @@ class ZmwPlanes:
     @property
     def width(self) -> int:
         return self.ccs.shape[0]
+
+    def without_subreads(self) -> "ZmwPlanes":
+        """The planes a ZMW without model windows still needs: ccs and
+        ccs_q; ``sub`` shrinks to [3, 0, W]."""
+        return dataclasses.replace(
+            self, sub=np.empty((3, 0, self.width), np.uint8),
+            strand=np.empty(0, np.uint8), sn=np.zeros(4, np.int16),
+        )
+
+
+def encode_ccs_qualities(qualities: Any) -> Optional[np.ndarray]:
+    """CCS qualities as ``uint8`` codes q + 1, or None when a value is not
+    an integer in -1..254 (the ZMW then keeps the host passthrough)."""
+    q = np.asarray(qualities)
+    if q.ndim != 1:
+        return None
+    if q.dtype.kind not in "iu":
+        if q.dtype.kind != "f" or not np.array_equal(q, np.floor(q)):
+            return None
+    if q.size and (q.min() < -1 or q.max() > 254):
+        return None
+    return (q.astype(np.int64) + 1).astype(np.uint8)
 
 
 def _encode_bases(bases: np.ndarray) -> np.ndarray:
@@ -131,6 +173,50 @@ def n_model_windows(z: Any) -> int:
     return 0
 
 
+def n_table_passthrough(z: Any) -> int:
+    """Skipped windows a ZmwWindows-like object carries as passthrough
+    table entries of its planes (not as ``skipped`` objects)."""
+    planes = getattr(z, "planes", None)
+    return 0 if planes is None else len(planes.pt_start)
+
+
+# Columns of a pt_tab row.
+PT_ZMW, PT_START, PT_W, PT_WIDTH, PT_DST = range(5)
+
+
+def validate_passthrough_table(
+    pt_tab: np.ndarray, zmw_widths: Sequence[int]
+) -> int:
+    """Host validator of a passthrough table against the widths W of the
+    packed ZMWs; returns the byte count of the passthrough region.
+
+    Raises ValueError unless, for every entry, zmw_index names a packed
+    ZMW, start >= 0, 1 <= w <= width, start + w <= W, dst_off is the
+    running sum of the widths before it, and the total stays below 2^31.
+    """
+    pt_tab = np.asarray(pt_tab)
+    _check(pt_tab.ndim == 2 and pt_tab.shape[1] == 5
+           and pt_tab.dtype in (np.int32, np.int64),
+           "pt_tab must be an integer [P, 5] table")
+    if not len(pt_tab):
+        return 0
+    tab = pt_tab.astype(np.int64)
+    zi, start, w, width, dst = tab.T
+    widths = np.asarray(zmw_widths, np.int64)
+    _check(bool(((zi >= 0) & (zi < len(widths))).all()),
+           "passthrough window of a ZMW that is not packed")
+    _check(bool((start >= 0).all()), "passthrough window with start < 0")
+    _check(bool(((w >= 1) & (w <= width)).all()),
+           "passthrough window with w outside 1..width")
+    _check(bool((start + w <= widths[zi]).all()),
+           "passthrough window ends past the ZMW width")
+    _check(bool((dst == np.cumsum(width) - width).all()),
+           "passthrough dst_off is not the running sum of the widths")
+    total = int(width.sum())
+    _check(total < 2**31, "passthrough region too large for int32 offsets")
+    return total
+
+
 @dataclasses.dataclass
 class FeaturizeBatch:
     """Planes and tables of one ZMW batch.
@@ -147,6 +233,14 @@ class FeaturizeBatch:
     in concatenation order. zmw_index -1 means the kernel writes zeros:
     tail padding, or a window of a fallback ZMW whose host ``rows`` the
     caller copies in (``fallback_idx`` / ``fallback_rows``).
+
+    With passthrough tables (passthrough_mode "device") the blob also
+    holds ``ccs_q`` uint8, laid out like ``ccs`` at the same offsets (zero
+    for a ZMW without one), and pt_tab int32 [P, 5]: (zmw_index, start, w,
+    width, dst_off) per skipped window, in ZMW order then window order;
+    dst_off is the running sum of ``width``, the window's offset inside
+    the ``n_pt_bytes`` passthrough region of the stitch buffer. Both are
+    empty otherwise.
     """
 
     blob: np.ndarray
@@ -163,6 +257,11 @@ class FeaturizeBatch:
     use_ccs_bq: bool
     fallback_idx: np.ndarray  # int64, ascending window indices
     fallback_rows: Optional[np.ndarray]  # int16 [len(fallback_idx), R, L]
+    ccs_q: np.ndarray = dataclasses.field(
+        default_factory=lambda: np.empty(0, np.uint8))
+    pt_tab: np.ndarray = dataclasses.field(
+        default_factory=lambda: np.empty((0, 5), np.int32))
+    n_pt_bytes: int = 0
 
     def fallback_range(self, lo: int, hi: int) -> Tuple[int, int]:
         """Slice of fallback_idx / fallback_rows inside windows [lo, hi)."""
@@ -199,9 +298,11 @@ def pack_batch(
     n_windows = 0
     layout = None  # (max_passes, max_length, use_ccs_bq)
     rows_shape = None
+    pt_parts: List[np.ndarray] = []
     for z in zmws:
         n = n_model_windows(z)
-        if not n:
+        n_pt = n_table_passthrough(z)
+        if not n and not n_pt:
             continue
         if z.rows is not None:
             rows = np.asarray(z.rows)
@@ -248,8 +349,33 @@ def pack_batch(
             tab[:, 1] = start
             tab[:, 2] = w
             win_parts.append(tab)
+            if p.ccs_q is not None:
+                _check(p.ccs_q.dtype == np.uint8 and p.ccs_q.shape == (W,),
+                       "ccs_q must be uint8 [W]")
+            if n_pt:
+                _check(p.ccs_q is not None,
+                       "passthrough table on a ZMW without ccs_q")
+                _check(np.shape(p.pt_w) == np.shape(p.pt_width) == (n_pt,),
+                       "pt_start, pt_w and pt_width must be [n_passthrough]")
+                pt = np.zeros((n_pt, 5), np.int64)
+                pt[:, PT_ZMW] = len(plane_zmws)
+                pt[:, PT_START] = p.pt_start
+                pt[:, PT_W] = p.pt_w
+                pt[:, PT_WIDTH] = p.pt_width
+                pt_parts.append(pt)
             plane_zmws.append(p)
         n_windows += n
+
+    if pt_parts:
+        pt_all = np.concatenate(pt_parts)
+        # The validator rejects width < 1 below, before dst_off is used.
+        pt_all[:, PT_DST] = np.cumsum(pt_all[:, PT_WIDTH]) - pt_all[
+            :, PT_WIDTH]
+    else:
+        pt_all = np.empty((0, 5), np.int64)
+    n_pt_bytes = validate_passthrough_table(
+        pt_all, [p.width for p in plane_zmws])
+    with_q = any(p.ccs_q is not None for p in plane_zmws)
 
     if layout is None:
         _check(rows_shape is not None or n_windows == 0, "no layout")
@@ -272,10 +398,13 @@ def pack_batch(
     sizes = [
         ("zmw_tab", np.int64, n_zmw * n_col),
         ("win_tab", np.int32, n_padded * 3),
+        ("pt_tab", np.int32, len(pt_all) * 5),
         ("ccs_bq", np.int16,
          sum(p.width for p in plane_zmws) if use_ccs_bq else 0),
         ("sub", np.uint8, sum(p.sub.size for p in plane_zmws)),
         ("ccs", np.uint8, sum(p.width for p in plane_zmws)),
+        ("ccs_q", np.uint8,
+         sum(p.width for p in plane_zmws) if with_q else 0),
     ]
     # Descending item size, so every view is aligned to its own type.
     offsets, total = {}, 0
@@ -309,6 +438,9 @@ def pack_batch(
         views["ccs"][ccs_off : ccs_off + W] = p.ccs
         if use_ccs_bq:
             views["ccs_bq"][ccs_off : ccs_off + W] = p.ccs_bq
+        if with_q:
+            views["ccs_q"][ccs_off : ccs_off + W] = (
+                0 if p.ccs_q is None else p.ccs_q)
         sub_off += p.sub.size
         ccs_off += W
     # Offsets inside the arrays: true by construction, checked anyway.
@@ -318,7 +450,10 @@ def pack_batch(
         win_tab[:n_windows] = np.concatenate(win_parts)
     win_tab[n_windows:, 0] = -1
     win_tab[n_windows:, 1:] = 0
+    pt_tab = views["pt_tab"].reshape(len(pt_all), 5)
+    pt_tab[:] = pt_all
     return FeaturizeBatch(
+        ccs_q=views["ccs_q"], pt_tab=pt_tab, n_pt_bytes=n_pt_bytes,
         blob=blob, offsets=offsets, zmw_tab=zmw_tab, win_tab=win_tab,
         ccs_bq=views["ccs_bq"], sub=views["sub"], ccs=views["ccs"],
         n_windows=n_windows, n_rows=n_rows, max_length=max_length,
@@ -410,3 +545,59 @@ def featurize_chunk_numpy(
     if k1 > k0:
         out[batch.fallback_idx[k0:k1] - lo] = batch.fallback_rows[k0:k1]
     return out
+
+
+def passthrough_fill_numpy(
+    ccs: np.ndarray,
+    ccs_q: np.ndarray,
+    zmw_tab: np.ndarray,
+    pt_tab: np.ndarray,
+    qual_lut: np.ndarray,
+    bases_out: np.ndarray,
+    quals_out: np.ndarray,
+) -> None:
+    """Numpy twin of the ``passthrough_fill`` kernel: fills the
+    passthrough region (``bases_out`` / ``quals_out``, uint8 [n]) from the
+    packed ``ccs`` / ``ccs_q`` planes and the passthrough table.
+
+    Entry (zmw_index, start, w, width, dst_off) writes ``width`` bytes at
+    ``dst_off``: the CCS ids / ``qual_lut[ccs_q]`` of columns [start,
+    start + w), then id 0 / ``qual_lut[0]``. Like the kernel it never
+    trusts the tables: an entry whose zmw_index is outside the ZMW table,
+    or whose ZMW's planes do not lie inside ``ccs`` / ``ccs_q``, is id 0
+    and quality 0 throughout; start is clamped to [0, W], w to [0,
+    min(width, W - start)]; only bytes inside [0, n) are written.
+    """
+    for name, a in (("ccs", ccs), ("ccs_q", ccs_q), ("qual_lut", qual_lut),
+                    ("bases_out", bases_out), ("quals_out", quals_out)):
+        if a.dtype != np.uint8 or a.ndim != 1:
+            raise ValueError(f"{name} must be flat uint8")
+    if qual_lut.shape != (256,):
+        raise ValueError("qual_lut must have 256 entries")
+    if bases_out.shape != quals_out.shape:
+        raise ValueError("bases_out and quals_out must be of equal length")
+    if zmw_tab.ndim != 2 or (len(zmw_tab) and zmw_tab.shape[1] < TAB_FIXED):
+        raise ValueError("zmw_tab must be [Z, >= 5]")
+    if pt_tab.ndim != 2 or pt_tab.shape[1] != 5:
+        raise ValueError("pt_tab must be [P, 5]")
+    n = len(bases_out)
+    n_src = min(len(ccs), len(ccs_q))
+    for zi, start, w, width, dst in pt_tab.astype(np.int64).tolist():
+        width = max(width, 0)
+        lo, hi = max(dst, 0), min(dst + width, n)
+        if hi <= lo:
+            continue
+        ids = np.zeros(width, np.uint8)
+        qvs = np.zeros(width, np.uint8)
+        if 0 <= zi < len(zmw_tab):
+            ccs_off = int(zmw_tab[zi, TAB_CCS_OFF])
+            W = int(zmw_tab[zi, TAB_W])
+            if ccs_off >= 0 and W >= 0 and ccs_off + W <= n_src:
+                start = min(max(start, 0), W)
+                w = min(max(w, 0), width, W - start)
+                src = slice(ccs_off + start, ccs_off + start + w)
+                ids[:w] = ccs[src]
+                qvs[:w] = qual_lut[ccs_q[src]]
+                qvs[w:] = qual_lut[0]
+        bases_out[lo:hi] = ids[lo - dst : hi - dst]
+        quals_out[lo:hi] = qvs[lo - dst : hi - dst]

@@ -5,6 +5,11 @@
              ZMW in both modes on a synthetic corpus (no model, no pool).
   --kernel   GPU: HIP-event time of window_featurize at N windows next to
              a device-to-device copy_ of an equally sized int16 tensor.
+  --worker --passthrough --skip_windows_above Q
+             the same worker numbers for passthrough_mode host vs device.
+  --passthrough-kernel
+             GPU: HIP-event time of passthrough_fill_into at N windows next
+             to a device-to-device copy_ of the same byte count.
 """
 import argparse
 import os
@@ -30,7 +35,16 @@ def worker_main(args):
             td, args.zmws, args.length, args.subreads, 3)
         dc_config = DcConfig(20, 100, False)
         for mode in ("host", "device", "host", "device"):
-            options = qi.InferenceOptions(featurize_mode=mode)
+            if args.passthrough:
+                # passthrough_mode host vs device under the device pipeline.
+                options = qi.InferenceOptions(
+                    featurize_mode="device", stitch_mode="device",
+                    passthrough_mode=mode,
+                    skip_windows_above=args.skip_windows_above)
+            else:
+                options = qi.InferenceOptions(
+                    featurize_mode=mode,
+                    skip_windows_above=args.skip_windows_above)
             proc_feeder, _ = pre_feeder.create_proc_feeder(
                 subreads_to_ccs=sub, ccs_bam=ccs, dc_config=dc_config,
                 defer_expansion=True,
@@ -49,7 +63,8 @@ def worker_main(args):
             print(f"{mode:6s}: {1e3 * work_s / n:7.2f} ms/ZMW worker, "
                   f"{1e3 * pickle_s / n:6.2f} ms/ZMW pickle round trip, "
                   f"{sum(map(len, blobs)) / n / 1e3:8.1f} kB pickled/ZMW, "
-                  f"{sum(z.n_model for z in outs) / n:.0f} model "
+                  f"{sum(z.n_model for z in outs) / n:.0f} model + "
+                  f"{sum(z.n_skipped for z in outs) / n:.0f} passthrough "
                   f"windows/ZMW ({n} ZMWs)")
 
 
@@ -108,10 +123,79 @@ def kernel_main(args):
           f"{c[2]:.3f}) = {gb / c[0] * 1e3:.0f} GB/s written")
 
 
+def passthrough_kernel_main(args):
+    import torch
+
+    from deepconsensus_amd import ops
+
+    ext = ops.get_ext(required=True)
+    L, W = 100, 15000
+    P = args.windows
+    rng = np.random.default_rng(0)
+    n_zmw = -(-P // (W // L))
+    tab = np.zeros((n_zmw, 5 + 20 + 4), np.int64)
+    tab[:, 1] = np.arange(n_zmw) * W
+    tab[:, 4] = W
+    pt = np.zeros((P, 5), np.int32)
+    pt[:, 0] = np.arange(P) // (W // L)
+    pt[:, 1] = (np.arange(P) % (W // L)) * L
+    pt[:, 2] = pt[:, 3] = L
+    pt[:, 4] = np.arange(P) * L
+    n = P * L
+    base = 7 * L  # the region starts at a multiple of row_length only
+    dev = [torch.from_numpy(a).cuda() for a in (
+        rng.integers(0, 5, n_zmw * W, dtype=np.uint8),
+        rng.integers(0, 95, n_zmw * W, dtype=np.uint8), tab, pt,
+        np.minimum(np.arange(256), 93).astype(np.uint8))]
+    acc = torch.empty((2, base + n), dtype=torch.uint8, device="cuda")
+    src = torch.randint(0, 5, (2, n), dtype=torch.uint8, device="cuda")
+    ms = {"kernel": [], "copy": []}
+
+    def once(name, fn):
+        a = torch.cuda.Event(enable_timing=True)
+        b = torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms[name].append(a.elapsed_time(b))
+
+    def kernel():
+        ext.passthrough_fill_into(*dev, acc[0, base:], acc[1, base:])
+
+    def copy():
+        acc[:, base:].copy_(src)
+
+    for _ in range(args.warmup):
+        kernel()
+        copy()
+    torch.cuda.synchronize()
+    for _ in range(args.repeats):  # alternating, one process
+        once("kernel", kernel)
+        once("copy", copy)
+    mb = 2 * n / 1e6
+    print(f"P={P} windows x {L} columns: {mb:.2f} MB written (both rows), "
+          f"{args.repeats} launches each after {args.warmup} warm-up, "
+          f"alternating")
+    for name, label in (("kernel", "passthrough_fill_into"),
+                        ("copy", "d2d copy_ [2, n]     ")):
+        v = ms[name]
+        med = statistics.median(v)
+        print(f"{label}: median {med * 1e3:.1f} us (min {min(v) * 1e3:.1f}, "
+              f"max {max(v) * 1e3:.1f}) = {mb / med:.1f} GB/s written")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--worker", action="store_true")
     ap.add_argument("--kernel", action="store_true")
+    ap.add_argument("--passthrough-kernel", action="store_true",
+                    help="GPU: passthrough_fill_into at N windows next to "
+                    "a device-to-device copy_ of the same bytes")
+    ap.add_argument("--passthrough", action="store_true",
+                    help="with --worker: compare passthrough_mode host and "
+                    "device (featurize and stitch mode device in both)")
+    ap.add_argument("--skip_windows_above", type=int, default=45)
     ap.add_argument("--zmws", type=int, default=20)
     ap.add_argument("--length", type=int, default=15000)
     ap.add_argument("--subreads", type=int, default=8)
@@ -123,6 +207,8 @@ def main():
         worker_main(args)
     if args.kernel:
         kernel_main(args)
+    if args.passthrough_kernel:
+        passthrough_kernel_main(args)
 
 
 if __name__ == "__main__":

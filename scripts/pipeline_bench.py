@@ -33,11 +33,30 @@ def main():
     ap.add_argument("--batch-size", type=int, default=2048)
     ap.add_argument("--batch-zmws", type=int, default=50)
     ap.add_argument("--device", default=None)
+    # The synthetic CCS qualities are uniform in 20..39: a 100-column
+    # window averages about Q26.2 (avg_phred), so 26 sends most windows
+    # through the CCS passthrough and 0 (the default here) none.
+    ap.add_argument("--skip_windows_above", type=int, default=0)
+    ap.add_argument("--stitch_mode", default=None)
+    ap.add_argument("--featurize_mode", default=None)
+    ap.add_argument("--passthrough_mode", default=None)
     args = ap.parse_args()
 
     import torch
 
     from deepconsensus_amd.inference import quick_inference as qi
+
+    # Model / passthrough window counts of the run, from the worker output.
+    n_windows = {"model": 0, "passthrough": 0}
+    for fn in ("run_model_on_zmws", "run_model_and_stitch_on_zmws"):
+        real = getattr(qi, fn)
+
+        def counting(zmws, runner, options, real=real):
+            n_windows["model"] += sum(z.n_model for z in zmws)
+            n_windows["passthrough"] += sum(z.n_skipped for z in zmws)
+            return real(zmws, runner, options)
+
+        setattr(qi, fn, counting)
 
     # Deterministic random-init weights: success/only_gaps outcome
     # counts are then stable for a given device RNG.
@@ -50,7 +69,11 @@ def main():
         out = os.path.join(td, "out.fastq")
         options = qi.InferenceOptions(
             batch_size=args.batch_size, batch_zmws=args.batch_zmws,
-            cpus=args.cpus, min_quality=0, skip_windows_above=0,
+            cpus=args.cpus, min_quality=0,
+            skip_windows_above=args.skip_windows_above,
+            stitch_mode=args.stitch_mode,
+            featurize_mode=args.featurize_mode,
+            passthrough_mode=args.passthrough_mode,
         )
         t0 = time.perf_counter()
         counter = qi.run(subreads_to_ccs=sub, ccs_bam=ccs,
@@ -62,6 +85,13 @@ def main():
         print(f"pipeline: {args.zmws / run_s:.2f} ZMW/s wall "
               f"({run_s:.1f}s, success={counter.success}, "
               f"cpus={args.cpus}, batch={args.batch_size})")
+        total = max(sum(n_windows.values()), 1)
+        print(f"windows: model={n_windows['model']} "
+              f"passthrough={n_windows['passthrough']} "
+              f"({100.0 * n_windows['passthrough'] / total:.1f}% "
+              f"passthrough), modes: stitch={qi.resolve_stitch_mode(options)}"
+              f" featurize={qi.resolve_featurize_mode(options)} "
+              f"passthrough={qi.resolve_passthrough_mode(options)}")
         # Per-stage main-thread time (preprocess overlaps via the prefetch
         # thread, so its visible share should be ~0 when pipelining works).
         stage_s = {}
