@@ -97,6 +97,13 @@ def _run_main(argv: List[str]) -> None:
                     "on CPU). device needs --featurize_mode device and "
                     "--stitch_mode device. Default: the DC_PASSTHROUGH_MODE "
                     "environment variable, else host")
+    ap.add_argument("--spacing_mode", default=None,
+                    choices=list(qi.SPACING_MODES),
+                    help="subread spacing: host (workers space every read "
+                    "and build the per-ZMW planes) or device (workers ship "
+                    "unspaced reads, the GPU builds the planes; numpy on "
+                    "CPU). device needs --featurize_mode device. Default: "
+                    "the DC_SPACING_MODE environment variable, else host")
     ap.add_argument("--use_only_gpu_index", type=int, default=None,
                     help="pin inference to this GPU index "
                     "(shorthand for --device cuda:N)")
@@ -125,6 +132,7 @@ def _run_main(argv: List[str]) -> None:
         stitch_mode=args.stitch_mode,
         featurize_mode=args.featurize_mode,
         passthrough_mode=args.passthrough_mode,
+        spacing_mode=args.spacing_mode,
     )
     if args.shard:
         i, n = args.shard.split("/")

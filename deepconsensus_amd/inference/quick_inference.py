@@ -38,6 +38,8 @@ from deepconsensus_amd.postprocess import stitch as stitch_utils
 from deepconsensus_amd.postprocess import stitch_device
 from deepconsensus_amd.preprocess import featurize_device
 from deepconsensus_amd.preprocess import feeder as pre_feeder
+from deepconsensus_amd.preprocess import spacing_device
+from deepconsensus_amd.preprocess import windows as windows_lib
 from deepconsensus_amd.preprocess.windows import DcConfig
 from deepconsensus_amd.utils import constants, phred
 
@@ -116,11 +118,18 @@ class InferenceOptions:
     # DCModelOutput, and fills the stitch buffer from the CCS planes on
     # the GPU. Only defined with featurize_mode and stitch_mode "device".
     passthrough_mode: Optional[str] = None
+    # Subread spacing: "host" | "device". None reads DC_SPACING_MODE
+    # (default "host"). "device" has the workers ship unspaced reads
+    # (preprocess/spacing_device.py) and builds the per-ZMW planes on the
+    # GPU instead of spacing every read in the worker. Only defined with
+    # featurize_mode "device".
+    spacing_mode: Optional[str] = None
 
 
 STITCH_MODES = ("serial", "pool", "device")
 FEATURIZE_MODES = ("host", "device")
 PASSTHROUGH_MODES = ("host", "device")
+SPACING_MODES = ("host", "device")
 
 
 def resolve_stitch_mode(options: InferenceOptions) -> str:
@@ -170,6 +179,26 @@ def resolve_passthrough_mode(options: InferenceOptions) -> str:
     return mode
 
 
+def resolve_spacing_mode(options: InferenceOptions) -> str:
+    """options.spacing_mode if set, else the DC_SPACING_MODE env knob.
+    "device" needs featurize mode "device"."""
+    mode = options.spacing_mode
+    if mode is None:
+        mode = os.environ.get("DC_SPACING_MODE", "host")
+    if mode not in SPACING_MODES:
+        raise ValueError(
+            f"spacing_mode must be one of {SPACING_MODES}, got {mode!r}"
+        )
+    if mode == "device":
+        featurize = resolve_featurize_mode(options)
+        if featurize != "device":
+            raise ValueError(
+                f"spacing_mode 'device' needs featurize_mode 'device', got "
+                f"featurize_mode {featurize!r}"
+            )
+    return mode
+
+
 @dataclasses.dataclass
 class ZmwWindows:
     """Worker output for one ZMW: model windows pre-stacked, skipped
@@ -196,7 +225,8 @@ class ZmwWindows:
     # plus a window table; ``rows`` is then None. passthrough_mode
     # "device": the planes also carry the skipped windows as a passthrough
     # table (``skipped`` is then empty), and stay when no window is
-    # model-bound.
+    # model-bound. spacing_mode "device": a spacing_device.ZmwUnspaced
+    # with the same tables stands here instead.
     planes: Optional[featurize_device.ZmwPlanes] = None
 
     @property
@@ -226,6 +256,22 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
     if isinstance(subreads, pre_feeder.ZmwJob):
         expand_counter = collections.Counter()
         subreads = subreads.materialize(expand_counter)
+    if (stage != DebugStage.DC_INPUT
+            and resolve_spacing_mode(options) == "device"
+            and isinstance(subreads, list)):
+        # No read is spaced here. None for a ZMW off this path: it is
+        # spaced below and ships planes, as in spacing_mode "host".
+        fallback_counter = collections.Counter()
+        unspaced = spacing_device.build_unspaced(
+            subreads[:-1], subreads[-1], dc_config, window_widths,
+            fallback_counter,
+        )
+        if unspaced is not None:
+            return _unspaced_zmw_windows(
+                zmw, unspaced, subreads[-1], options, expand_counter
+            )
+        expand_counter = (expand_counter or collections.Counter())
+        expand_counter.update(fallback_counter)
     dc_whole = pre_feeder.subreads_to_dc_example(
         subreads=subreads,
         ccs_seqname=zmw,
@@ -254,11 +300,8 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
     if planes is not None:
         # Same windows, counters and triage as below; a model-bound
         # window is two table entries instead of an [R, L] matrix.
-        win_start: List[int] = []
-        win_w: List[int] = []
         # Device passthrough: a skipped window is a table entry as well,
         # when the ZMW's CCS qualities fit the uint8 code.
-        pt: List[Tuple[int, int, int, int]] = []
         if resolve_passthrough_mode(options) == "device":
             planes.ccs_q = featurize_device.encode_ccs_qualities(
                 ccs.base_quality_scores
@@ -266,39 +309,16 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
             if (planes.ccs_q is not None
                     and planes.ccs_q.shape != planes.ccs.shape):
                 planes.ccs_q = None
-        for spec in dc_whole.iter_window_specs():
-            if _skip_window(spec.overflow, spec.bq, options):
-                if planes.ccs_q is not None:
-                    pt.append(
-                        (spec.start, spec.w, spec.width, spec.window_pos)
-                    )
-                    continue
-                ccs_ids = np.zeros(spec.width, np.uint8)
-                ccs_ids[: spec.w] = planes.ccs[
-                    spec.start : spec.start + spec.w
-                ]
-                skipped.append(_passthrough_output(
-                    ccs_ids, spec.bq, spec.window_pos, dc_whole.name,
-                    ccs.ec, ccs.np_num_passes, ccs.rq, ccs.rg, options,
-                ))
-                continue
-            win_start.append(spec.start)
-            win_w.append(spec.w)
-            window_pos.append(spec.window_pos)
-        planes.win_start = np.asarray(win_start, np.int32)
-        planes.win_w = np.asarray(win_w, np.int32)
-        if pt:
-            cols = np.asarray(pt, np.int64).T
-            planes.pt_start, planes.pt_w, planes.pt_width = (
-                c.astype(np.int32) for c in cols[:3]
-            )
-            planes.pt_pos = cols[3]
-        else:
+        has_model, has_table, window_pos, skipped = _triage_windows(
+            planes, dc_whole.iter_window_specs(), planes.ccs,
+            planes.ccs_q is not None, dc_whole.name, ccs, options,
+        )
+        if not has_table:
             planes.ccs_q = None  # nothing reads it
-        if not win_start:
+        if not has_model:
             # Without model windows only the passthrough table needs the
             # planes, and of them only ccs and ccs_q.
-            planes = planes.without_subreads() if pt else None
+            planes = planes.without_subreads() if has_table else None
     else:
         for f in dc_whole.iter_feature_dicts(
             pw_max=featurize_device.PW_MAX, ip_max=featurize_device.IP_MAX,
@@ -319,6 +339,85 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
         name=zmw,
         window_pos=np.asarray(window_pos, np.int64),
         rows=np.stack(model_rows) if model_rows else None,
+        skipped=skipped,
+        counter=counter,
+        ec=ccs.ec, np_num_passes=ccs.np_num_passes, rq=ccs.rq, rg=ccs.rg,
+        planes=planes,
+    )
+
+
+def _triage_windows(planes, specs, ccs_ids, table_ok, name, ccs,
+                    options: InferenceOptions):
+    """Skip triage over the window specs of one ZMW on the plane path,
+    shared by spaced planes and unspaced ZMWs: fills the window table and
+    the passthrough table of ``planes`` and returns (has model windows,
+    has table entries, window_pos of the model windows, skipped objects).
+
+    ``ccs_ids`` are the spaced CCS base ids. A skipped window becomes a
+    passthrough table entry when ``table_ok`` (device passthrough and CCS
+    qualities that fit the uint8 code), an object otherwise.
+    """
+    win_start: List[int] = []
+    win_w: List[int] = []
+    window_pos: List[int] = []
+    skipped: List[stitch_utils.DCModelOutput] = []
+    pt: List[Tuple[int, int, int, int]] = []
+    for spec in specs:
+        if _skip_window(spec.overflow, spec.bq, options):
+            if table_ok:
+                pt.append(
+                    (spec.start, spec.w, spec.width, spec.window_pos)
+                )
+                continue
+            ids = np.zeros(spec.width, np.uint8)
+            ids[: spec.w] = ccs_ids[spec.start : spec.start + spec.w]
+            skipped.append(_passthrough_output(
+                ids, spec.bq, spec.window_pos, name,
+                ccs.ec, ccs.np_num_passes, ccs.rq, ccs.rg, options,
+            ))
+            continue
+        win_start.append(spec.start)
+        win_w.append(spec.w)
+        window_pos.append(spec.window_pos)
+    planes.win_start = np.asarray(win_start, np.int32)
+    planes.win_w = np.asarray(win_w, np.int32)
+    if pt:
+        cols = np.asarray(pt, np.int64).T
+        planes.pt_start, planes.pt_w, planes.pt_width = (
+            c.astype(np.int32) for c in cols[:3]
+        )
+        planes.pt_pos = cols[3]
+    return bool(win_start), bool(pt), window_pos, skipped
+
+
+def _unspaced_zmw_windows(zmw, unspaced, ccs, options: InferenceOptions,
+                          expand_counter) -> ZmwWindows:
+    """ZmwWindows of a ZMW that ships unspaced (spacing_mode "device"):
+    windows, counters and triage from the CCS row, which follows from
+    ``ins_max`` before any read is spaced."""
+    ccs_ids, ccs_idx, ccs_bq, ccs_width = spacing_device.spaced_ccs_row(
+        unspaced, ccs.ccs_idx
+    )
+    counter = collections.Counter()
+    specs = windows_lib.window_specs(
+        unspaced.max_length, unspaced.W, ccs_width, ccs_bq, ccs_idx,
+        windows_lib.fixed_window_widths(ccs_width, unspaced.max_length),
+        counter,
+    )
+    has_model, has_table, window_pos, skipped = _triage_windows(
+        unspaced, specs, ccs_ids,
+        resolve_passthrough_mode(options) == "device", zmw, ccs, options,
+    )
+    unspaced.want_q = has_table
+    planes = unspaced
+    if not has_model:
+        planes = unspaced.without_subreads() if has_table else None
+    if expand_counter:
+        counter.update(expand_counter)
+    return ZmwWindows(
+        name=zmw,
+        window_pos=np.asarray(window_pos, np.int64),
+        rows=None,
         skipped=skipped,
         counter=counter,
         ec=ccs.ec, np_num_passes=ccs.np_num_passes, rq=ccs.rq, rg=ccs.rg,
@@ -531,6 +630,7 @@ class _ModelChunks:
     def _init_planes(self) -> None:
         if not self.native:
             self.batch = featurize_device.pack_batch(self.packed_zmws)
+            spacing_device.space_batch_numpy(self.batch)
         else:
             device = self.runner.device
             staging: List[torch.Tensor] = []
@@ -539,18 +639,28 @@ class _ModelChunks:
                 staging.append(
                     torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
                 )
-                return staging[0].numpy()
+                return staging[-1].numpy()
 
             # With the graph every chunk is batch_size table entries:
             # the tail is padded with -1 (zero) windows once, here.
             self.batch = batch = featurize_device.pack_batch(
                 self.packed_zmws,
                 pad_multiple=self.batch_size if self.use_graph else 1,
-                alloc=alloc,
+                alloc=alloc, device_planes=True,
             )
             blob = staging[0].to(device, non_blocking=True)
+            planes = None
+            if batch.device_planes:
+                # Unspaced ZMWs: the plane region is born on the device,
+                # zero-filled, in pack_batch's layout.
+                planes = torch.zeros(batch.plane_nbytes, dtype=torch.uint8,
+                                     device=device)
 
             def view(name: str, array: np.ndarray) -> torch.Tensor:
+                if planes is not None and name in batch.plane_layout:
+                    lo, dtype, count = batch.plane_layout[name]
+                    flat = planes[lo : lo + count * np.dtype(dtype).itemsize]
+                    return flat.view(getattr(torch, np.dtype(dtype).name))
                 lo = batch.offsets[name]
                 flat = blob[lo : lo + array.nbytes]
                 return flat.view(getattr(torch, array.dtype.name))
@@ -568,6 +678,8 @@ class _ModelChunks:
                 self.dev[1], view("ccs_q", batch.ccs_q), self.dev[3],
                 view("pt_tab", batch.pt_tab).view(batch.pt_tab.shape),
             )
+            if batch.spacing is not None:
+                self._space_on_device(view, staging[1])
             if batch.fallback_rows is not None:
                 self.fallback_rows = torch.from_numpy(
                     batch.fallback_rows
@@ -577,6 +689,35 @@ class _ModelChunks:
                 ).to(device)
         self.n_model = self.batch.n_windows
         self.row_length = self.batch.max_length
+
+    def _space_on_device(self, view, staged: torch.Tensor) -> None:
+        """Fills the device planes of the unspaced ZMWs: one copy of the
+        packed reads, then the subread_space kernel, on the stream of the
+        kernels that read the planes. ZMWs spaced on the host have their
+        planes copied into their slices."""
+        batch, sp = self.batch, self.batch.spacing
+        sp_blob = staged.to(self.runner.device, non_blocking=True)
+
+        def sp_view(name: str, array: np.ndarray, dtype) -> torch.Tensor:
+            lo = sp.offsets[name]
+            return sp_blob[lo : lo + array.nbytes].view(dtype)
+
+        sub, ccs, ccs_bq, zmw_tab = self.dev
+        ccs_q = self.pt_dev[1]
+        targets = dict(sub=sub, ccs=ccs, ccs_bq=ccs_bq, ccs_q=ccs_q)
+        for name, off, array in batch.host_planes:
+            targets[name][off : off + array.size].copy_(
+                torch.from_numpy(array))
+        ins_max = sp_view("ins_max", sp.ins_max, torch.int16)
+        self.runner.ext.subread_space_into(
+            sp_view("src", sp.src, torch.uint8), ins_max,
+            sp_view("sp_tab", sp.sp_tab, torch.int64).view(sp.sp_tab.shape),
+            sp_view("read_tab", sp.read_tab, torch.int64).view(
+                sp.read_tab.shape),
+            zmw_tab, torch.empty(ins_max.numel(), dtype=torch.int32,
+                                 device=self.runner.device),
+            sub, ccs, ccs_q, ccs_bq, batch.use_ccs_bq,
+        )
 
     def chunk(self, i: int) -> Tuple[torch.Tensor, int]:
         """(rows_t, n_valid) for windows [i, i + batch_size): the model
@@ -1000,6 +1141,7 @@ def run(
     options = options or InferenceOptions()
     resolve_featurize_mode(options)  # a bad value fails here, not in a worker
     resolve_passthrough_mode(options)  # so does a mode combination
+    resolve_spacing_mode(options)
     if resolve_stitch_mode(options) == "device":
         stitch_device.check_max_base_quality(options.max_base_quality)
 

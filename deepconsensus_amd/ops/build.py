@@ -33,6 +33,7 @@ _SRCS = [
     os.path.join(_OPS_DIR, "hip", "stitch_compact.hip"),
     os.path.join(_OPS_DIR, "hip", "window_featurize.hip"),
     os.path.join(_OPS_DIR, "hip", "passthrough_fill.hip"),
+    os.path.join(_OPS_DIR, "hip", "subread_space.hip"),
 ]
 EXT_NAME = "dc_hip_kernels"
 

@@ -262,8 +262,20 @@ void passthrough_fill_into(at::Tensor ccs, at::Tensor ccs_q,
                            at::Tensor zmw_tab, at::Tensor pt_tab,
                            at::Tensor qual_lut, at::Tensor bases_out,
                            at::Tensor quals_out);
+// Defined in subread_space.hip.
+void subread_space_into(at::Tensor src, at::Tensor ins_max,
+                        at::Tensor sp_tab, at::Tensor read_tab,
+                        at::Tensor zmw_tab, at::Tensor col_ref,
+                        at::Tensor sub, at::Tensor ccs, at::Tensor ccs_q,
+                        at::Tensor ccs_bq, bool use_ccs_bq);
+int64_t subread_space_tile();
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("subread_space_into", &subread_space_into,
+        "Device subread spacing: unspaced reads + ins_max -> caller-owned "
+        "zero-filled sub / ccs / ccs_q / ccs_bq planes");
+  m.def("subread_space_tile", &subread_space_tile,
+        "Scan tile (elements) of subread_space_into");
   m.def("passthrough_fill_into", &passthrough_fill_into,
         "Device CCS passthrough: skipped windows of the packed planes -> "
         "caller-owned base-id and QV rows of the stitch buffer");

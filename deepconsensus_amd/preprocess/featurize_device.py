@@ -262,6 +262,24 @@ class FeaturizeBatch:
     pt_tab: np.ndarray = dataclasses.field(
         default_factory=lambda: np.empty((0, 5), np.int32))
     n_pt_bytes: int = 0
+    # spacing_mode "device": the unspaced ZMWs of the batch
+    # (spacing_device.SpacingBatch); their planes are zero until the
+    # subread_space kernel or its twin has run. ``plane_layout`` maps
+    # ccs_bq / sub / ccs / ccs_q to (byte offset, dtype, element count)
+    # inside the plane region. With ``device_planes`` the region is not part
+    # of ``blob`` (the four host views are empty): the caller allocates it
+    # zero-filled on the device and copies in ``host_planes``, the (name,
+    # element offset, array) pieces of the ZMWs that were spaced on the
+    # host.
+    spacing: Any = None
+    plane_layout: dict = dataclasses.field(default_factory=dict)
+    device_planes: bool = False
+    host_planes: list = dataclasses.field(default_factory=list)
+
+    @property
+    def plane_nbytes(self) -> int:
+        return sum(np.dtype(dtype).itemsize * count
+                   for _, dtype, count in self.plane_layout.values())
 
     def fallback_range(self, lo: int, hi: int) -> Tuple[int, int]:
         """Slice of fallback_idx / fallback_rows inside windows [lo, hi)."""
@@ -274,10 +292,25 @@ def _check(cond: bool, message: str) -> None:
         raise ValueError(f"pack_batch: {message}")
 
 
+def _has_bq(p: Any) -> bool:
+    """Whether a ZmwPlanes or ZmwUnspaced carries the ccs_bq plane."""
+    if getattr(p, "unspaced", False):
+        return bool(p.use_ccs_bq)
+    return p.ccs_bq is not None
+
+
+def _wants_q(p: Any) -> bool:
+    """Whether the ccs_q plane of a ZmwPlanes or ZmwUnspaced is filled."""
+    if getattr(p, "unspaced", False):
+        return bool(p.want_q)
+    return p.ccs_q is not None
+
+
 def pack_batch(
     zmws: Sequence[Any],
     pad_multiple: int = 1,
     alloc: Optional[Callable[[int], np.ndarray]] = None,
+    device_planes: bool = False,
 ) -> FeaturizeBatch:
     """Packs the model windows of a ZMW batch for the featurize kernel.
 
@@ -286,6 +319,12 @@ def pack_batch(
     window table with -1 entries to a multiple of it (fixed-shape graph
     replays). ``alloc(nbytes)`` returns the ``uint8`` buffer to pack
     into (pinned memory, say); numpy allocates otherwise.
+
+    ``planes`` may also be a spacing_device.ZmwUnspaced: the ZMW gets the
+    same table rows and the same, zero-filled, slices of the plane arrays,
+    and its reads are packed into ``FeaturizeBatch.spacing`` (a second
+    ``alloc`` call). ``device_planes`` then leaves the plane arrays out of
+    the host buffer (see FeaturizeBatch).
 
     Raises ValueError when a table entry would make the kernel read
     outside a plane or when the ZMWs disagree on the layout.
@@ -317,21 +356,24 @@ def pack_batch(
             win_parts[-1][:, 1:] = 0
         else:
             p = z.planes
+            unspaced = getattr(p, "unspaced", False)
             this = (int(p.max_passes), int(p.max_length),
-                    p.ccs_bq is not None)
+                    _has_bq(p))
             _check(layout in (None, this),
                    f"ZMWs disagree on (max_passes, max_length, "
                    f"use_ccs_bq): {layout} and {this}")
             layout = this
             n_sub, W = p.n_sub, p.width
-            _check(p.sub.dtype == np.uint8 and p.sub.shape == (3, n_sub, W),
-                   "sub must be uint8 [3, n_sub, W]")
-            _check(p.ccs.dtype == np.uint8, "ccs must be uint8")
+            if not unspaced:
+                _check(p.sub.dtype == np.uint8
+                       and p.sub.shape == (3, n_sub, W),
+                       "sub must be uint8 [3, n_sub, W]")
+                _check(p.ccs.dtype == np.uint8, "ccs must be uint8")
             _check(n_sub <= p.max_passes,
                    f"n_sub={n_sub} exceeds max_passes={p.max_passes}")
             _check(p.strand.shape == (n_sub,), "strand must be [n_sub]")
             _check(np.shape(p.sn) == (4,), "sn must be [4]")
-            if p.ccs_bq is not None:
+            if not unspaced and p.ccs_bq is not None:
                 _check(p.ccs_bq.dtype == np.int16
                        and p.ccs_bq.shape == (W,),
                        "ccs_bq must be int16 [W]")
@@ -349,11 +391,11 @@ def pack_batch(
             tab[:, 1] = start
             tab[:, 2] = w
             win_parts.append(tab)
-            if p.ccs_q is not None:
+            if not unspaced and p.ccs_q is not None:
                 _check(p.ccs_q.dtype == np.uint8 and p.ccs_q.shape == (W,),
                        "ccs_q must be uint8 [W]")
             if n_pt:
-                _check(p.ccs_q is not None,
+                _check(_wants_q(p),
                        "passthrough table on a ZMW without ccs_q")
                 _check(np.shape(p.pt_w) == np.shape(p.pt_width) == (n_pt,),
                        "pt_start, pt_w and pt_width must be [n_passthrough]")
@@ -375,7 +417,10 @@ def pack_batch(
         pt_all = np.empty((0, 5), np.int64)
     n_pt_bytes = validate_passthrough_table(
         pt_all, [p.width for p in plane_zmws])
-    with_q = any(p.ccs_q is not None for p in plane_zmws)
+    with_q = any(_wants_q(p) for p in plane_zmws)
+    unspaced_zmws = [(i, p) for i, p in enumerate(plane_zmws)
+                     if getattr(p, "unspaced", False)]
+    device_planes = bool(device_planes and unspaced_zmws)
 
     if layout is None:
         _check(rows_shape is not None or n_windows == 0, "no layout")
@@ -395,17 +440,24 @@ def pack_batch(
     n_zmw = len(plane_zmws)
     n_padded = -(-n_windows // pad_multiple) * pad_multiple
     n_col = TAB_FIXED + max_passes + 4
-    sizes = [
-        ("zmw_tab", np.int64, n_zmw * n_col),
-        ("win_tab", np.int32, n_padded * 3),
-        ("pt_tab", np.int32, len(pt_all) * 5),
+    plane_sizes = [
         ("ccs_bq", np.int16,
          sum(p.width for p in plane_zmws) if use_ccs_bq else 0),
-        ("sub", np.uint8, sum(p.sub.size for p in plane_zmws)),
+        ("sub", np.uint8, sum(3 * p.n_sub * p.width for p in plane_zmws)),
         ("ccs", np.uint8, sum(p.width for p in plane_zmws)),
         ("ccs_q", np.uint8,
          sum(p.width for p in plane_zmws) if with_q else 0),
     ]
+    plane_layout, plane_total = {}, 0
+    for name, dtype, count in plane_sizes:
+        plane_layout[name] = (plane_total, dtype, count)
+        plane_total += count * np.dtype(dtype).itemsize
+    sizes = [
+        ("zmw_tab", np.int64, n_zmw * n_col),
+        ("win_tab", np.int32, n_padded * 3),
+        ("pt_tab", np.int32, len(pt_all) * 5),
+    ] + [(name, dtype, 0 if device_planes else count)
+         for name, dtype, count in plane_sizes]
     # Descending item size, so every view is aligned to its own type.
     offsets, total = {}, 0
     for name, dtype, count in sizes:
@@ -425,8 +477,10 @@ def pack_batch(
     win_tab = views["win_tab"].reshape(n_padded, 3)
     zmw_tab[:] = 0
     sub_off = ccs_off = 0
+    host_planes: List[Tuple[str, int, np.ndarray]] = []
     for i, p in enumerate(plane_zmws):
         n_sub, W = p.n_sub, p.width
+        sub_size = 3 * n_sub * W
         zmw_tab[i, TAB_SUB_OFF] = sub_off
         zmw_tab[i, TAB_CCS_OFF] = ccs_off
         zmw_tab[i, TAB_BQ_OFF] = ccs_off if use_ccs_bq else 0
@@ -434,18 +488,39 @@ def pack_batch(
         zmw_tab[i, TAB_W] = W
         zmw_tab[i, TAB_FIXED : TAB_FIXED + n_sub] = p.strand
         zmw_tab[i, TAB_FIXED + max_passes :] = p.sn
-        views["sub"][sub_off : sub_off + p.sub.size] = p.sub.reshape(-1)
-        views["ccs"][ccs_off : ccs_off + W] = p.ccs
-        if use_ccs_bq:
-            views["ccs_bq"][ccs_off : ccs_off + W] = p.ccs_bq
-        if with_q:
-            views["ccs_q"][ccs_off : ccs_off + W] = (
-                0 if p.ccs_q is None else p.ccs_q)
-        sub_off += p.sub.size
+        if getattr(p, "unspaced", False):
+            # Zero until the spacing kernel (or its twin) fills them.
+            pieces = [("sub", sub_off, sub_size, 0), ("ccs", ccs_off, W, 0)]
+            if use_ccs_bq:
+                pieces.append(("ccs_bq", ccs_off, W, 0))
+            if with_q:
+                pieces.append(("ccs_q", ccs_off, W, 0))
+        else:
+            pieces = [("sub", sub_off, sub_size, p.sub.reshape(-1)),
+                      ("ccs", ccs_off, W, p.ccs)]
+            if use_ccs_bq:
+                pieces.append(("ccs_bq", ccs_off, W, p.ccs_bq))
+            if with_q and p.ccs_q is not None:
+                pieces.append(("ccs_q", ccs_off, W, p.ccs_q))
+            elif with_q:
+                pieces.append(("ccs_q", ccs_off, W, 0))
+        for name, off, count, value in pieces:
+            if not device_planes:
+                views[name][off : off + count] = value
+            elif isinstance(value, np.ndarray) and count:
+                host_planes.append((name, off, np.ascontiguousarray(value)))
+        sub_off += sub_size
         ccs_off += W
     # Offsets inside the arrays: true by construction, checked anyway.
-    _check(sub_off == views["sub"].size and ccs_off == views["ccs"].size,
+    _check(sub_off == plane_layout["sub"][2]
+           and ccs_off == plane_layout["ccs"][2],
            "plane offsets do not add up to the packed arrays")
+    spacing = None
+    if unspaced_zmws:
+        from deepconsensus_amd.preprocess import spacing_device
+
+        spacing = spacing_device.pack_spacing(
+            unspaced_zmws, zmw_tab, sub_off, ccs_off, alloc=alloc)
     if n_windows:
         win_tab[:n_windows] = np.concatenate(win_parts)
     win_tab[n_windows:, 0] = -1
@@ -453,6 +528,8 @@ def pack_batch(
     pt_tab = views["pt_tab"].reshape(len(pt_all), 5)
     pt_tab[:] = pt_all
     return FeaturizeBatch(
+        spacing=spacing, plane_layout=plane_layout,
+        device_planes=device_planes, host_planes=host_planes,
         ccs_q=views["ccs_q"], pt_tab=pt_tab, n_pt_bytes=n_pt_bytes,
         blob=blob, offsets=offsets, zmw_tab=zmw_tab, win_tab=win_tab,
         ccs_bq=views["ccs_bq"], sub=views["sub"], ccs=views["ccs"],

@@ -107,6 +107,57 @@ class WindowSpec:
     bq: np.ndarray
 
 
+def fixed_window_widths(ccs_width: int, example_width: int) -> List[int]:
+    """Fixed-width windows covering ``ccs_width`` spaced columns."""
+    num_full = int(ccs_width / example_width)
+    if ccs_width % example_width > 0:
+        num_full += 1
+    return [example_width] * num_full
+
+
+def window_specs(max_length: int, W: int, ccs_width: int,
+                 ccs_bq_all: np.ndarray, ccs_idx_all: np.ndarray,
+                 window_widths: List[int], counter: collections.Counter):
+    """The inference windows of a spaced ZMW from its CCS row alone:
+    width W, ``ccs_width`` (last non-gap CCS column + 1), the spaced CCS
+    qualities and CCS indices (-1 in gap columns). Fills ``counter``;
+    windows without any CCS index are counted and not yielded. Shared by
+    DcExample.iter_window_specs and the unspaced path
+    (preprocess/spacing_device.py), which knows the CCS row before any
+    read is spaced."""
+    start_pos = 0
+    for window_width in window_widths:
+        counter[f"example_width_bucket_{window_width}"] += 1
+        if start_pos > ccs_width:
+            break
+        s, e = start_pos, min(start_pos + window_width, W)
+        start_pos += window_width
+        w_idx = ccs_idx_all[s:e]
+        valid = w_idx >= 0
+        if not valid.any():
+            counter["n_examples_no_ccs_idx"] += 1
+            continue
+        overflow = window_width > max_length
+        if overflow:
+            counter["n_examples_overflow"] += 1
+            # Read.pad still applies: an overflow window clipped at
+            # the ZMW end shorter than max_length pads back up to it.
+            width = max(e - s, max_length)
+        else:
+            counter["n_examples_skip_large_windows_keep"] += 1
+            width = max_length
+        w = e - s
+        bq = ccs_bq_all[s:e]
+        if w < width:  # Read.pad pads quality scores with -1
+            bq_full = np.full(width, -1, ccs_bq_all.dtype)
+            bq_full[:w] = bq
+            bq = bq_full
+        yield WindowSpec(
+            start=s, w=w, width=width, overflow=overflow,
+            window_pos=int(w_idx[valid].min()), bq=bq,
+        )
+
+
 @dataclasses.dataclass
 class DcExample:
     """Container generating model inputs from spaced reads."""
@@ -209,10 +260,7 @@ class DcExample:
                 ccs_calculated_width += window_width_spaced
             assert ccs_calculated_width == self.ccs_width
         else:
-            num_full = int(self.ccs_width / example_width)
-            if self.ccs_width % example_width > 0:
-                num_full += 1
-            window_widths = [example_width] * num_full
+            window_widths = fixed_window_widths(self.ccs_width, example_width)
         return window_widths
 
     def iter_examples(self):
@@ -265,42 +313,12 @@ class DcExample:
         ``self.counter``; windows without any CCS index are counted and
         not yielded.
         """
-        max_length = self.config.max_length
-        W = self.width
-        ccs_bq_all = np.asarray(self.ccs.base_quality_scores)
-        ccs_idx_all = self.ccs.ccs_idx
         self.counter = collections.Counter()
-        start_pos = 0
-        for window_width in self.calculate_windows(max_length):
-            self.counter[f"example_width_bucket_{window_width}"] += 1
-            if start_pos > self.ccs_width:
-                break
-            s, e = start_pos, min(start_pos + window_width, W)
-            start_pos += window_width
-            w_idx = ccs_idx_all[s:e]
-            valid = w_idx >= 0
-            if not valid.any():
-                self.counter["n_examples_no_ccs_idx"] += 1
-                continue
-            overflow = window_width > max_length
-            if overflow:
-                self.counter["n_examples_overflow"] += 1
-                # Read.pad still applies: an overflow window clipped at
-                # the ZMW end shorter than max_length pads back up to it.
-                width = max(e - s, max_length)
-            else:
-                self.counter["n_examples_skip_large_windows_keep"] += 1
-                width = max_length
-            w = e - s
-            bq = ccs_bq_all[s:e]
-            if w < width:  # Read.pad pads quality scores with -1
-                bq_full = np.full(width, -1, ccs_bq_all.dtype)
-                bq_full[:w] = bq
-                bq = bq_full
-            yield WindowSpec(
-                start=s, w=w, width=width, overflow=overflow,
-                window_pos=int(w_idx[valid].min()), bq=bq,
-            )
+        return window_specs(
+            self.config.max_length, self.width, self.ccs_width,
+            np.asarray(self.ccs.base_quality_scores), self.ccs.ccs_idx,
+            self.calculate_windows(self.config.max_length), self.counter,
+        )
 
     @property
     def is_evenly_spaced_inference(self) -> bool:

@@ -10,8 +10,17 @@
   --passthrough-kernel
              GPU: HIP-event time of passthrough_fill_into at N windows next
              to a device-to-device copy_ of the same byte count.
+  --worker --spacing_mode host|device
+             the same worker numbers for one spacing_mode under
+             featurize_mode device (alternate the two by hand); the host
+             pass is split into decode, expand, spacing + put_spacing, and
+             DcExample + build_planes + triage.
+  --spacing-kernel
+             GPU: HIP-event time of subread_space_into on --zmws ZMWs next
+             to a device-to-device copy_ of the bytes it writes.
 """
 import argparse
+import collections
 import os
 import pickle
 import statistics
@@ -66,6 +75,139 @@ def worker_main(args):
                   f"{sum(z.n_model for z in outs) / n:.0f} model + "
                   f"{sum(z.n_skipped for z in outs) / n:.0f} passthrough "
                   f"windows/ZMW ({n} ZMWs)")
+
+
+def spacing_worker_main(args):
+    """Worker cost of one spacing_mode: --passes passes over the corpus,
+    the first one cold."""
+    from deepconsensus_amd.dcio import bam
+    from deepconsensus_amd.inference import quick_inference as qi
+    from deepconsensus_amd.preprocess import feeder as pre_feeder
+    from deepconsensus_amd.preprocess import read as read_lib
+    from deepconsensus_amd.preprocess.windows import DcConfig
+    from deepconsensus_amd.utils.synth import make_synth_bams
+
+    mode = args.spacing_mode
+    split = collections.defaultdict(float)
+
+    def timed(name, fn):
+        def wrapper(*a, **kw):
+            t0 = time.perf_counter()
+            try:
+                return fn(*a, **kw)
+            finally:
+                split[name] += time.perf_counter() - t0
+        return wrapper
+
+    # Nested timers: decode and expand run inside materialize, spacing
+    # inside subreads_to_dc_example; the rest of preprocess_one_zmw is
+    # DcExample + build_planes + triage (host) or build_unspaced + triage
+    # (device).
+    bam.decode_record = timed("decode", bam.decode_record)
+    pre_feeder.expand_clip_indent = timed(
+        "expand", pre_feeder.expand_clip_indent)
+    pre_feeder.space_out_subreads = timed(
+        "spacing+put_spacing", read_lib.space_out_subreads)
+
+    with tempfile.TemporaryDirectory() as td:
+        sub, ccs, _ = make_synth_bams(
+            td, args.zmws, args.length, args.subreads, 3)
+        dc_config = DcConfig(20, 100, False)
+        options = qi.InferenceOptions(
+            featurize_mode="device", stitch_mode="device",
+            passthrough_mode=args.passthrough_mode, spacing_mode=mode,
+            skip_windows_above=args.skip_windows_above)
+        for p in range(args.passes):
+            proc_feeder, _ = pre_feeder.create_proc_feeder(
+                subreads_to_ccs=sub, ccs_bam=ccs, dc_config=dc_config,
+                defer_expansion=True,
+            )
+            jobs = [(zmw, subreads, dcc, ww, options)
+                    for subreads, zmw, dcc, _, ww in proc_feeder()]
+            split.clear()
+            t0 = time.perf_counter()
+            outs = [qi.preprocess_one_zmw(j) for j in jobs]
+            work_s = time.perf_counter() - t0
+            blobs = [pickle.dumps(z, pickle.HIGHEST_PROTOCOL) for z in outs]
+            n = len(jobs)
+            rest = work_s - sum(split.values())
+            parts = ", ".join(f"{k} {1e3 * v / n:.2f}"
+                              for k, v in sorted(split.items()))
+            unspaced = sum(getattr(z.planes, "unspaced", False)
+                           for z in outs)
+            print(f"spacing={mode:6s} pass {p}: {1e3 * work_s / n:7.2f} "
+                  f"ms/ZMW worker [{parts}, rest {1e3 * rest / n:.2f}], "
+                  f"{sum(map(len, blobs)) / n / 1e3:8.1f} kB pickled/ZMW, "
+                  f"{unspaced}/{n} ZMWs unspaced")
+
+
+def spacing_kernel_main(args):
+    """subread_space_into on a packed batch of --zmws unspaced ZMWs next
+    to a device-to-device copy_ of the plane bytes it fills."""
+    import torch
+
+    from deepconsensus_amd import ops
+    from deepconsensus_amd.inference import quick_inference as qi
+    from deepconsensus_amd.preprocess import featurize_device as fd
+    from deepconsensus_amd.preprocess import feeder as pre_feeder
+    from deepconsensus_amd.preprocess.windows import DcConfig
+    from deepconsensus_amd.utils.synth import make_synth_bams
+
+    ext = ops.get_ext(required=True)
+    with tempfile.TemporaryDirectory() as td:
+        sub, ccs, _ = make_synth_bams(
+            td, args.zmws, args.length, args.subreads, 3)
+        dc_config = DcConfig(20, 100, False)
+        options = qi.InferenceOptions(
+            featurize_mode="device", stitch_mode="device",
+            spacing_mode="device", skip_windows_above=0)
+        proc_feeder, _ = pre_feeder.create_proc_feeder(
+            subreads_to_ccs=sub, ccs_bam=ccs, dc_config=dc_config,
+            defer_expansion=True)
+        outs = [qi.preprocess_one_zmw((zmw, subreads, dcc, ww, options))
+                for subreads, zmw, dcc, _, ww in proc_feeder()]
+    batch = fd.pack_batch(outs)
+    sp = batch.spacing
+    dev = [torch.from_numpy(a.copy()).cuda() for a in (
+        sp.src, sp.ins_max.view(np.int16), sp.sp_tab, sp.read_tab,
+        batch.zmw_tab)]
+    col_ref = torch.empty(len(sp.ins_max), dtype=torch.int32, device="cuda")
+    planes = [torch.zeros(len(a), dtype=getattr(torch, a.dtype.name),
+                          device="cuda")
+              for a in (batch.sub, batch.ccs, batch.ccs_q, batch.ccs_bq)]
+    n_written = sum(3 * int(n) for n in sp.read_tab[:, 2]) + int(
+        sp.sp_tab[:, 3].sum())
+    n_planes = sum(p.numel() * p.element_size() for p in planes)
+    src_copy = torch.empty(n_planes, dtype=torch.uint8, device="cuda")
+    dst_copy = torch.empty_like(src_copy)
+
+    def timed(fn):
+        a, b = torch.cuda.Event(True), torch.cuda.Event(True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e3
+
+    run = lambda: ext.subread_space_into(  # noqa: E731
+        *dev, col_ref, *planes, batch.use_ccs_bq)
+    copy = lambda: dst_copy.copy_(src_copy)  # noqa: E731
+    for _ in range(args.warmup):
+        run()
+        copy()
+    t = {"kernel": [], "copy": []}
+    for _ in range(args.repeats):  # alternating, one process
+        t["kernel"].append(timed(run))
+        t["copy"].append(timed(copy))
+    print(f"{len(outs)} ZMWs x {args.subreads} subreads x {args.length} bp:"
+          f" {len(sp.src) / 1e6:.2f} MB unspaced source, {n_written / 1e6:.2f}"
+          f" MB scattered into {n_planes / 1e6:.2f} MB of planes; "
+          f"{args.repeats} launches each after {args.warmup} warm-up")
+    for name, label in (("kernel", "subread_space_into (both phases)"),
+                        ("copy", "copy_ of the plane bytes")):
+        v = sorted(t[name])
+        print(f"  {label:34s} median {statistics.median(v):8.1f} us  "
+              f"min {v[0]:8.1f}  max {v[-1]:8.1f}")
 
 
 def kernel_main(args):
@@ -195,6 +337,16 @@ def main():
     ap.add_argument("--passthrough", action="store_true",
                     help="with --worker: compare passthrough_mode host and "
                     "device (featurize and stitch mode device in both)")
+    ap.add_argument("--spacing_mode", default=None,
+                    choices=["host", "device"],
+                    help="with --worker: worker cost and its split for this "
+                    "spacing_mode (featurize_mode device)")
+    ap.add_argument("--spacing-kernel", action="store_true",
+                    help="GPU: subread_space_into on --zmws ZMWs next to "
+                    "a copy_ of the plane bytes")
+    ap.add_argument("--passthrough_mode", default="host",
+                    choices=["host", "device"])
+    ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--skip_windows_above", type=int, default=45)
     ap.add_argument("--zmws", type=int, default=20)
     ap.add_argument("--length", type=int, default=15000)
@@ -203,6 +355,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=50)
     args = ap.parse_args()
+    if args.worker and args.spacing_mode:
+        spacing_worker_main(args)
+        return
+    if args.spacing_kernel:
+        spacing_kernel_main(args)
+        return
     if args.worker:
         worker_main(args)
     if args.kernel:

@@ -40,6 +40,7 @@ def main():
     ap.add_argument("--stitch_mode", default=None)
     ap.add_argument("--featurize_mode", default=None)
     ap.add_argument("--passthrough_mode", default=None)
+    ap.add_argument("--spacing_mode", default=None)
     args = ap.parse_args()
 
     import torch
@@ -74,6 +75,7 @@ def main():
             stitch_mode=args.stitch_mode,
             featurize_mode=args.featurize_mode,
             passthrough_mode=args.passthrough_mode,
+            spacing_mode=args.spacing_mode,
         )
         t0 = time.perf_counter()
         counter = qi.run(subreads_to_ccs=sub, ccs_bam=ccs,
@@ -91,7 +93,8 @@ def main():
               f"({100.0 * n_windows['passthrough'] / total:.1f}% "
               f"passthrough), modes: stitch={qi.resolve_stitch_mode(options)}"
               f" featurize={qi.resolve_featurize_mode(options)} "
-              f"passthrough={qi.resolve_passthrough_mode(options)}")
+              f"passthrough={qi.resolve_passthrough_mode(options)} "
+              f"spacing={qi.resolve_spacing_mode(options)}")
         # Per-stage main-thread time (preprocess overlaps via the prefetch
         # thread, so its visible share should be ~0 when pipelining works).
         stage_s = {}
