@@ -257,6 +257,10 @@ class InferenceRunner:
             # v3 (256-row tiles, register-resident h) measures fastest;
             # DC_FFN_V3=0 drops back to v2/v1.
             self.ffn_v3 = _os.environ.get("DC_FFN_V3", "1") != "0"
+            # v5 = v3's chunk loop in a persistent grid (bitwise-equal
+            # outputs, profiles/r07_persistent_ffn.md); DC_FFN_V5=0 falls
+            # through to the v3/v2/v1 chain.
+            self.ffn_v5 = _os.environ.get("DC_FFN_V5", "1") != "0"
 
             if self.ffn_fused_ok:
                 for i, l in enumerate(model.layers):
@@ -378,7 +382,12 @@ class InferenceRunner:
                             280, False, lw["alpha_attn"],
                         )
                     with trace.range("K9_fused_ffn"):
-                        if self.ffn_v3:
+                        if self.ffn_v5:
+                            flat = self.ext.fused_ffn_v5(
+                                flat, lw["w1_v2"], lw["w2_pad"],
+                                lw["b2_f32"], lw["alpha_ffn"],
+                            )
+                        elif self.ffn_v3:
                             flat = self.ext.fused_ffn_v3(
                                 flat, lw["w1_v2"], lw["w2_pad"],
                                 lw["b2_f32"], lw["alpha_ffn"],

@@ -34,6 +34,7 @@ _SRCS = [
     os.path.join(_OPS_DIR, "hip", "window_featurize.hip"),
     os.path.join(_OPS_DIR, "hip", "passthrough_fill.hip"),
     os.path.join(_OPS_DIR, "hip", "subread_space.hip"),
+    os.path.join(_OPS_DIR, "hip", "fused_ffn_v5.hip"),
 ]
 EXT_NAME = "dc_hip_kernels"
 

@@ -187,6 +187,8 @@ at::Tensor fused_ffn_v2(at::Tensor x, at::Tensor w1, at::Tensor w2,
                         at::Tensor b2, double alpha);
 at::Tensor fused_ffn_v3(at::Tensor x, at::Tensor w1, at::Tensor w2,
                         at::Tensor b2, double alpha);
+at::Tensor fused_ffn_v5(at::Tensor x, at::Tensor w1, at::Tensor w2,
+                        at::Tensor b2, double alpha, int64_t max_blocks);
 void embed_grad(at::Tensor rows, at::Tensor grad_out, at::Tensor row_shift,
                 at::Tensor row_vocab, at::Tensor row_tbase,
                 at::Tensor row_width, at::Tensor row_col,
@@ -319,6 +321,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused FFN v2: glds-pipelined weights, bias folded into W1");
   m.def("fused_ffn_v3", &fused_ffn_v3,
         "Fused FFN v3: 256-row tiles, register-resident h (swapped B1)");
+  m.def("fused_ffn_v5", &fused_ffn_v5,
+        "Fused FFN v5: v3 chunk loop in a persistent grid (continuous "
+        "weight stream, direct x fragments, 16-B epilogue); max_blocks "
+        "caps the grid, 0 = one block per CU",
+        pybind11::arg("x"), pybind11::arg("w1"), pybind11::arg("w2"),
+        pybind11::arg("b2"), pybind11::arg("alpha"),
+        pybind11::arg("max_blocks") = 0);
   m.def("embed_grad", &embed_grad,
         "Fused embedding-stack backward (training, all tables, one pass)");
   m.def("fused_linear", &fused_linear,
