@@ -131,6 +131,57 @@ def build_gather_tables(model: EncoderOnlyLearnedValuesTransformer):
     return table_flat, row_shift, row_vocab, chunk_cnt, chunk_entries.reshape(-1)
 
 
+# Input widths fused_condense (K3+K4) is instantiated for: the concat
+# widths of the served layouts, max_passes 20/32 without/with ccs_bq.
+_CONDENSE_WIDTHS = (560, 568, 872, 880)
+
+
+def condense_image_stride(k: int) -> Optional[int]:
+    """Row stride WS(K) of the fused_condense weight image, or None.
+
+    WS = 16 * ceil(K / 16) + 8: the kernel's B-side read of the last
+    granule's upper half (columns 16*NG - 8 .. 16*NG - 1) must stay inside
+    the row's own zero-filled image even when K is 8 mod 16. Returns None
+    for a width the kernel is not instantiated for.
+    """
+    if k not in _CONDENSE_WIDTHS:
+        return None
+    return 16 * (-(-k // 16)) + 8
+
+
+def build_condense_image(weight: torch.Tensor) -> torch.Tensor:
+    """Zero-padded bf16 weight image [Npad, WS] for fused_condense.
+
+    weight is the condenser Linear weight [N, K]; row n of the image holds
+    weight[n, :K] rounded to bf16, everything else is zero. Npad is N
+    rounded up to a multiple of 64 (the kernel's output-column chunk).
+    """
+    n, k = weight.shape
+    ws = condense_image_stride(k)
+    if ws is None:
+        raise ValueError(
+            f"fused_condense supports widths {_CONDENSE_WIDTHS}, got {k}"
+        )
+    npad = -(-n // 64) * 64
+    img = torch.zeros(npad, ws, dtype=torch.bfloat16)
+    img[:n, :k] = weight.detach().to(torch.bfloat16)
+    return img.contiguous()
+
+
+def fused_condense_enabled(k: int, value: Optional[str]) -> bool:
+    """Resolves DC_FUSED_CONDENSE (value; None = unset) for concat width k.
+
+    unset or "1": fused at the production width 560 only; "0": never;
+    "wide": fused at every width condense_image_stride() supports. Any
+    other value behaves like unset.
+    """
+    if value == "0":
+        return False
+    if value == "wide":
+        return condense_image_stride(k) is not None
+    return k == 560
+
+
 class InferenceRunner:
     """Runs window batches through the model, emitting base ids + QVs."""
 
@@ -187,20 +238,20 @@ class InferenceRunner:
             if model.add_pos_encoding
             else None
         )
-        # fused_condense (K3+K4): weight image [Npad, 568] (row n =
+        # fused_condense (K3+K4): weight image [Npad, WS] (row n =
         # condenser.weight[n], LDS row stride) + fp32 pos table fused into
-        # the epilogue. Production width only; DC_FUSED_CONDENSE=0 falls
-        # back to hipBLASLt + separate add.
+        # the epilogue. Production width (560) by default;
+        # DC_FUSED_CONDENSE=wide also takes 568/872/880, =0 falls back to
+        # hipBLASLt + separate add.
         import os as _os
 
         self.cond_img = None
         self.pos_f32 = None
         cw = model.condenser.weight.detach()
-        if cw.shape[1] == 560 and _os.environ.get("DC_FUSED_CONDENSE") != "0":
-            npad = -(-cw.shape[0] // 64) * 64
-            img = torch.zeros(npad, 568, dtype=bf16)
-            img[: cw.shape[0], :560] = cw.to(bf16)
-            self.cond_img = img.contiguous().to(dev)
+        if fused_condense_enabled(
+            cw.shape[1], _os.environ.get("DC_FUSED_CONDENSE")
+        ):
+            self.cond_img = build_condense_image(cw).to(dev)
             if model.add_pos_encoding:
                 self.pos_f32 = (
                     model.pos_encoding.detach().float().contiguous().to(dev)
