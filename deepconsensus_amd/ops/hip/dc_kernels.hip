@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void fused_ln_head_qv_kernel(
   const T* xi = x + (size_t)n * H;
 
   // Per-lane partial sums over dims lane, lane+64, ...
-  float sum = 0.f, sumsq = 0.f;
+  float sum = 0.f;
   float xv[8];  // H <= 512 supported
   int nd = 0;
   for (int d = lane; d < H; d += 64, ++nd) {
@@ -62,15 +62,22 @@ __global__ __launch_bounds__(256) void fused_ln_head_qv_kernel(
     else v = xi[d];
     xv[nd] = v;
     sum += v;
-    sumsq += v * v;
   }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    sum += __shfl_xor(sum, off, 64);
-    sumsq += __shfl_xor(sumsq, off, 64);
-  }
+  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
   const float mean = sum / H;
-  const float var = sumsq / H - mean * mean;
+  // Two-pass variance over the register-resident row: the one-pass
+  // sumsq/H - mean^2 cancels catastrophically on near-constant rows
+  // (offset >> spread) and can go negative, making rstd NaN.
+  float sq = 0.f;
+  nd = 0;
+  for (int d = lane; d < H; d += 64, ++nd) {
+    const float dv = xv[nd] - mean;
+    sq += dv * dv;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off, 64);
+  const float var = sq / H;
   const float rstd = rsqrtf(var + 1e-6f);
 
   // Head dots: 5 logits.

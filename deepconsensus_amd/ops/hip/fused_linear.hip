@@ -184,11 +184,19 @@ at::Tensor fused_linear(at::Tensor x, at::Tensor w, at::Tensor bias,
   const int K = xc.size(-1);
   const int M = xc.numel() / K;
   TORCH_CHECK(K == K1, "fused_linear requires width-280 input");
+  // The kernel streams w as a raw row-major bf16 image straight from its
+  // data pointer: no copy is made, so the layout is checked, not fixed up.
+  TORCH_CHECK(w.is_cuda() && w.dtype() == at::kBFloat16,
+              "w must be bf16 on device");
+  TORCH_CHECK(w.dim() == 2 && w.is_contiguous(), "w must be contiguous 2-D");
   const int Npad = w.size(0);
   TORCH_CHECK(w.size(1) == W_STRIDE && Npad % NC == 0,
               "w must be [Npad (mult of 64), 296]");
   const int N = (int)n_out;
-  TORCH_CHECK(N <= Npad, "n_out exceeds padded weight rows");
+  TORCH_CHECK(N > 0 && N <= Npad, "n_out exceeds padded weight rows");
+  // Copy-out writes 16-B granules of 8 columns; every caller's width is a
+  // multiple of 8 (840, 280), anything else would misalign the stores.
+  TORCH_CHECK(N % 8 == 0, "n_out must be a multiple of 8");
   TORCH_CHECK(!residual || N == K1, "residual requires N == 280");
   const bf16* resid_ptr = nullptr;
   at::Tensor rc;
