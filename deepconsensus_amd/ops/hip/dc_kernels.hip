@@ -213,6 +213,9 @@ std::vector<at::Tensor> alignment_dp_bwd(at::Tensor grad_out,
 std::vector<at::Tensor> alignment_metric_counts(
     at::Tensor yt, at::Tensor yp, at::Tensor yt_len, at::Tensor yp_len,
     double ms, double mp, double go, double ge);
+std::vector<at::Tensor> alignment_calib(
+    at::Tensor label, at::Tensor bases, at::Tensor quals,
+    double ms, double mp, double go, double ge);
 at::Tensor ffn_ablate(at::Tensor x, at::Tensor w1, at::Tensor w2,
                       at::Tensor b2, double alpha, int64_t mode);
 at::Tensor fused_ffn_v4(at::Tensor x, at::Tensor w1, at::Tensor w2,
@@ -345,6 +348,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Alignment-loss wavefront DP backward (K13 VJP)");
   m.def("alignment_metric_counts", &alignment_metric_counts,
         "Device AlignmentMetric (K14): affine NW + backtrace counts");
+  m.def("alignment_calib", &alignment_calib,
+        "Window QV calibration (K14+K15): in-kernel compaction, affine NW "
+        "with LDS directions, per-base class + per-QV match/mismatch table");
   m.def("banded_attn_train_fwd", &banded_attn_train_fwd,
         "Training banded attention forward (saves band softmax P)");
   m.def("banded_attn_mfma_train_fwd", &banded_attn_mfma_train_fwd,
