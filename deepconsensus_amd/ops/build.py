@@ -24,7 +24,6 @@ _SRCS = [
     os.path.join(_OPS_DIR, "hip", "embed_grad.hip"),
     os.path.join(_OPS_DIR, "hip", "alignment_metric.hip"),
     os.path.join(_OPS_DIR, "hip", "ffn_ablate.hip"),
-    os.path.join(_OPS_DIR, "hip", "fused_ffn_v4.hip"),
     os.path.join(_OPS_DIR, "hip", "banded_attn_train.hip"),
     os.path.join(_OPS_DIR, "hip", "banded_attn_bwd_mfma.hip"),
     os.path.join(_OPS_DIR, "hip", "fused_condense.hip"),

@@ -218,8 +218,6 @@ std::vector<at::Tensor> alignment_calib(
     double ms, double mp, double go, double ge);
 at::Tensor ffn_ablate(at::Tensor x, at::Tensor w1, at::Tensor w2,
                       at::Tensor b2, double alpha, int64_t mode);
-at::Tensor fused_ffn_v4(at::Tensor x, at::Tensor w1, at::Tensor w2,
-                        at::Tensor b2, double alpha);
 std::vector<at::Tensor> banded_attn_train_fwd(
     at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor mask,
     int64_t win, double p_drop);
@@ -364,8 +362,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "CU) -> packed dqkv");
   m.def("banded_attn_train_bwd", &banded_attn_train_bwd,
         "Training banded attention backward (band-local dS -> dq,dk,dv)");
-  m.def("fused_ffn_v4", &fused_ffn_v4,
-        "Fused FFN v4: B1 on 16x16x32 MFMAs (4 independent chains)");
   m.def("ffn_ablate", &ffn_ablate,
         "fused_ffn_v3 ablation probe (0 full, 1 B1-only, 2 B2-only, "
         "3 loads-only) — perf diagnosis");

@@ -1,7 +1,9 @@
 // Training FFN pair for gfx950: fused forward and fused dgrad, both
-// instances of the fused_ffn_v3 structure (256-row tiles, register-
+// sequencings of the tile core in ffn_tile.h (256-row tiles, register-
 // resident 2048-wide intermediate via swapped-B1 + T12 repack, glds
-// double-buffered weight streaming).
+// double-buffered weight streaming) with fused_ffn_v3's one-shot
+// prologue, chunk loop and 2-byte epilogue. This file owns what happens
+// to the intermediate between B1 and B2.
 //
 // Reference semantics: ffn_layer.py:69-87 — h = relu(x@W1^T + b1);
 // hd = dropout(h); y = hd@W2^T + b2 — and its autograd transpose.
@@ -29,57 +31,9 @@
 #include <ATen/hip/HIPContext.h>
 #endif
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-
-using bf16 = __hip_bfloat16;
+#include "ffn_tile.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int BM = 256;
-constexpr int K1 = 280;
-constexpr int K1P = 296;        // x-image / B1-weight row stride
-constexpr int BIAS_COL = 287;
-constexpr int NC = 64;
-constexpr int NHID = 2048;
-constexpr int NCHUNK = NHID / NC;
-constexpr int W2_STRIDE = 72;
-constexpr int W2_ROWS = 288;
-constexpr int NOUT = 280;
-
-constexpr int W1_ELEMS = NC * K1P;
-constexpr int W2_ELEMS = W2_ROWS * W2_STRIDE;
-constexpr int W1_CHUNKS = W1_ELEMS * 2 / 1024;
-constexpr int W2_GRAN = W2_ROWS * 9;
-constexpr int W2_CHUNKS = (W2_GRAN + 63) / 64;
-
-constexpr int OFF_W1 = 0;
-constexpr int OFF_W2 = 2 * W1_ELEMS;
-constexpr int OFF_SCRATCH = OFF_W2 + 2 * W2_ELEMS;
-constexpr int LDS_ELEMS = OFF_SCRATCH + 1024;
-
-__device__ __forceinline__ void glds16(const bf16* gsrc, bf16* ldst) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) unsigned*)gsrc,
-      (__attribute__((address_space(3))) unsigned*)ldst, 16, 0, 0);
-}
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-__device__ __forceinline__ int lane_recompute() {
-  int l;
-  asm volatile(
-      "v_mbcnt_lo_u32_b32 %0, -1, 0\n\t"
-      "v_mbcnt_hi_u32_b32 %0, -1, %0"
-      : "=v"(l));
-  return l;
-}
 
 // 32-bit mix (lowbias32 family) of (seed, m row, hidden idx) -> [0,1).
 // Deterministic given the host-drawn seed; statistical quality is ample
@@ -108,98 +62,13 @@ __global__ __launch_bounds__(512, 1) void ffn_train_kernel(
     unsigned long long seed) {
   __shared__ __attribute__((aligned(16))) bf16 smem[LDS_ELEMS];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31;
-  const int hi = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int m0 = blockIdx.x * BM;
 
-  // Stage x (FWD) / dy (DGRAD) through the W2[1] LDS region; the bias
-  // constant at col 287 is harmless for DGRAD (its B1 image keeps that
-  // column zero).
+  // Stage x (FWD) / dy (DGRAD); the bias constant at col 287 is harmless
+  // for DGRAD (its B1 image keeps that column zero).
   bf16x8 af[18];
-  {
-    bf16* ximg = &smem[OFF_W2 + W2_ELEMS];
-    for (int pass = 0; pass < 4; ++pass) {
-      __syncthreads();
-      for (int idx = tid; idx < 64 * 37; idx += 512) {
-        const int r = idx / 37, q4 = idx % 37;
-        const int row = 64 * pass + r;
-        uint4 v = {};
-        const bool rv = (m0 + row) < M;
-        if (rv && 8 * q4 + 8 <= K1) {
-          v = *reinterpret_cast<const uint4*>(
-              x + (size_t)(m0 + row) * K1 + 8 * q4);
-        } else if (rv && 8 * q4 + 7 == BIAS_COL) {
-          v.w = 0x3f800000u;
-        }
-        *reinterpret_cast<uint4*>(&ximg[r * K1P + 8 * q4]) = v;
-      }
-      __syncthreads();
-      if ((wave >> 1) == pass) {
-        const int r_local = 32 * (wave & 1) + c;
-#pragma unroll
-        for (int s = 0; s < 18; ++s) {
-          af[s] = *reinterpret_cast<const bf16x8*>(
-              &ximg[r_local * K1P + 16 * s + 8 * hi]);
-        }
-      }
-    }
-  }
-
-  // The glds LDS destination is wave-uniform and reaches the hardware
-  // through M0. Force it into an SGPR with an explicit readfirstlane:
-  // under register pressure (the dgrad instantiations) the allocator
-  // otherwise materializes it in a VGPR, SPILLS it, and rebuilds M0 from
-  // a scratch reload under a partial exec mask — when the reloading lane
-  // differs from the spilling lane, M0 is garbage and the weight DMA
-  // deposits at arbitrary LDS offsets (measured: nondeterministic NaN
-  // corruption in MODE 1/2 while MODE 0 happened to allocate cleanly).
-  // Lane id is re-derived (volatile v_mbcnt) inside each lambda and in
-  // the epilogue: the kernel-top `lane`/`c`/`hi` otherwise stay live
-  // across the whole chunk loop and are what the allocator spills.
-  auto issue_w1 = [&](int chunk, int buf) {
-    const int ln = lane_recompute();
-    const bf16* src = w1 + (size_t)chunk * W1_ELEMS;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      const int ck = wave + i * 8;
-      if (ck < W1_CHUNKS) {
-        const int dst_off = __builtin_amdgcn_readfirstlane(
-            OFF_W1 + buf * W1_ELEMS + ck * 512);
-        glds16(src + ck * 512 + ln * 8, &smem[dst_off]);
-      }
-    }
-  };
-  auto issue_w2 = [&](int chunk, int buf) {
-    const int ln = lane_recompute();
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const int ck = wave + i * 8;
-      const int g = ck * 64 + ln;
-      if (g < W2_GRAN) {
-        const int row = g / 9, sub = g % 9;
-        const int k8 = sub == 8 ? 0 : sub;
-        const int dst_off = __builtin_amdgcn_readfirstlane(
-            OFF_W2 + buf * W2_ELEMS + ck * 512);
-        glds16(w2 + (size_t)row * NHID + chunk * NC + 8 * k8,
-               &smem[dst_off]);
-      }
-    }
-  };
-
-  issue_w1(0, 0);
-  issue_w2(0, 0);
-  // lgkmcnt(0) is load-bearing: the af ds_reads issued in the staging
-  // pass are lgkm-tracked, and a raw s_barrier does NOT drain counters
-  // (__syncthreads would). Without it a wave can pass the barrier with
-  // af reads still in flight while another wave's chunk-1 glds
-  // overwrites the staging region (W2[1]) — a nondeterministic af
-  // corruption measured in the dgrad instantiation (a handful of NaN
-  // elements per million, schedule-dependent).
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  stage_x_issue_chunk0(smem, x, w1, w2, m0, M, wave, af);
 
   // Wave-uniform hd bases (m0, wave are SGPRs): the compiler keeps these
   // in scalar registers, so only a 32-bit per-lane offset is ever live
@@ -220,24 +89,15 @@ __global__ __launch_bounds__(512, 1) void ffn_train_kernel(
     const int buf = chunk & 1;
     const bool more = chunk + 1 < NCHUNK;
     if (more) {
-      issue_w1(chunk + 1, buf ^ 1);
-      issue_w2(chunk + 1, buf ^ 1);
+      issue_w1(smem, w1, wave, chunk + 1, buf ^ 1);
+      issue_w2(smem, w2, wave, chunk + 1, buf ^ 1);
     }
     const bf16* w1buf = &smem[OFF_W1 + buf * W1_ELEMS];
     const bf16* w2buf = &smem[OFF_W2 + buf * W2_ELEMS];
 
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      f32x16 acc = {};
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int s = 0; s < 18; ++s) {
-        const bf16x8 wfr = *reinterpret_cast<const bf16x8*>(
-            &w1buf[(32 * t + c) * K1P + 16 * s + 8 * hi]);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfr, af[s], acc,
-                                                      0, 0, 0);
-      }
-      __builtin_amdgcn_s_setprio(0);
+      f32x16 acc = b1_step(w1buf, af, t, c, hi);
       __builtin_amdgcn_sched_barrier(0);  // fence: keep B1 state local
       // MFMA D-register read hazard: the cvt_pk inline asm below reads
       // acc; in MODE 0 the ~48 relu VALU ops provide the required
@@ -270,20 +130,7 @@ __global__ __launch_bounds__(512, 1) void ffn_train_kernel(
         }
       }
       bf16x8 pa[2];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const unsigned x0 = cvt_pk_bf16(acc[8 * s + 0], acc[8 * s + 1]);
-        const unsigned y0 = cvt_pk_bf16(acc[8 * s + 2], acc[8 * s + 3]);
-        const unsigned x1 = cvt_pk_bf16(acc[8 * s + 4], acc[8 * s + 5]);
-        const unsigned y1 = cvt_pk_bf16(acc[8 * s + 6], acc[8 * s + 7]);
-        const auto rx = __builtin_amdgcn_permlane32_swap(x0, x1, false,
-                                                         false);
-        const auto ry = __builtin_amdgcn_permlane32_swap(y0, y1, false,
-                                                         false);
-        unsigned u[4] = {(unsigned)rx[0], (unsigned)ry[0], (unsigned)rx[1],
-                         (unsigned)ry[1]};
-        pa[s] = *reinterpret_cast<const bf16x8*>(u);
-      }
+      t12_repack(acc, pa);
 
       // In the repacked (B2 A-fragment) layout, lane (c, hi) holds row
       // (32*wave + c), k-span 64*chunk + 32*t + 16*s + 8*hi — so the
@@ -345,19 +192,7 @@ __global__ __launch_bounds__(512, 1) void ffn_train_kernel(
       }
 
       __builtin_amdgcn_sched_barrier(0);  // fence: store addrs die here
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-#pragma unroll
-        for (int ct = 0; ct < 9; ++ct) {
-          const int ocol = min(32 * ct + c, NOUT - 1);
-          const bf16x8 wfr = *reinterpret_cast<const bf16x8*>(
-              &w2buf[ocol * W2_STRIDE + 32 * t + 16 * s + 8 * hi]);
-          oacc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              pa[s], wfr, oacc[ct], 0, 0, 0);
-        }
-      }
-      __builtin_amdgcn_s_setprio(0);
+      b2_step(w2buf, pa, oacc, t, c, hi);
     }
 
     if (more) {
@@ -368,23 +203,10 @@ __global__ __launch_bounds__(512, 1) void ffn_train_kernel(
 
   // Epilogue: plain y (+b2 in FWD); the ReZero residual/post-dropout
   // stay in the wrapper (they are part of its autograd graph).
-  const int lne = lane_recompute();
-  const int ce = lne & 31;
-  const int hie = lne >> 5;
-#pragma unroll
-  for (int ct = 0; ct < 9; ++ct) {
-    const int col = 32 * ct + ce;
-    if (col >= NOUT) continue;
-    const float bias = (MODE == 0) ? b2[col] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * hie + 32 * wave;
-      if (m0 + row < M) {
-        out[(size_t)(m0 + row) * K1 + col] =
-            __float2bfloat16(oacc[ct][r] + bias);
-      }
-    }
-  }
+  store_tile_2b(out, oacc, m0, M, wave,
+                [&](int col, size_t, float acc) {
+                  return acc + ((MODE == 0) ? b2[col] : 0.f);
+                });
 }
 
 }  // namespace
@@ -467,19 +289,15 @@ std::vector<at::Tensor> ffn_train_dgrad_impl(at::Tensor dy, at::Tensor hd,
   const float p = (float)p_drop;
   dim3 grid((M + BM - 1) / BM);
   hipStream_t stream = at::hip::getCurrentHIPStream();
-  auto launch = [&](auto mode_t) {
-    hipLaunchKernelGGL((ffn_train_kernel<decltype(mode_t)::value>), grid,
-                       dim3(512), 0, stream,
-                       reinterpret_cast<bf16*>(dyc.data_ptr()),
-                       reinterpret_cast<bf16*>(w2t.data_ptr()),
-                       reinterpret_cast<bf16*>(w1t.data_ptr()), nullptr,
-                       reinterpret_cast<bf16*>(dx.data_ptr()),
-                       reinterpret_cast<bf16*>(dh.data_ptr()),
-                       reinterpret_cast<bf16*>(hdc.data_ptr()), M, p,
-                       p < 1.f ? 1.f / (1.f - p) : 0.f, 0ull);
-  };
-  if (nomask) launch(std::integral_constant<int, 2>{});
-  else launch(std::integral_constant<int, 1>{});
+  hipLaunchKernelGGL(nomask ? ffn_train_kernel<2> : ffn_train_kernel<1>,
+                     grid, dim3(512), 0, stream,
+                     reinterpret_cast<bf16*>(dyc.data_ptr()),
+                     reinterpret_cast<bf16*>(w2t.data_ptr()),
+                     reinterpret_cast<bf16*>(w1t.data_ptr()), nullptr,
+                     reinterpret_cast<bf16*>(dx.data_ptr()),
+                     reinterpret_cast<bf16*>(dh.data_ptr()),
+                     reinterpret_cast<bf16*>(hdc.data_ptr()), M, p,
+                     p < 1.f ? 1.f / (1.f - p) : 0.f, 0ull);
   return {dx, dh};
 }
 

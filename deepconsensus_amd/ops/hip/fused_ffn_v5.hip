@@ -1,10 +1,11 @@
-// Fused FFN v5 for gfx950: fused_ffn_v3's chunk loop inside a persistent
-// grid, with the per-tile work around the loop removed or overlapped.
+// Fused FFN v5 for gfx950: the tile core of ffn_tile.h inside a persistent
+// grid, with the per-tile work around the chunk loop removed or overlapped.
 //
 // Same math, weight layouts and accumulation order as fused_ffn_v3.hip
-// (W1 [2048, 296] with b1 in column 287, W2 padded [320, 2048], fp32 b2);
-// the MFMA / ds_read sequence of the chunk loop is v3's, untouched. What
-// changes is everything a one-shot v3 block pays serially per 256-row tile:
+// (W1 [2048, 296] with b1 in column 287, W2 padded [320, 2048], fp32 b2):
+// both kernels run the same shared B1 / repack / B2 steps per chunk, so the
+// two agree bitwise. What this kernel owns is everything a one-shot v3
+// block pays serially per 256-row tile:
 //  * persistent grid: one block per CU walks tiles blockIdx.x, +gridDim.x,
 //    ... instead of ~25 launch/drain rounds of one-shot blocks;
 //  * continuous weight stream: the double-buffered glds rotation runs
@@ -27,37 +28,12 @@
 #include <ATen/hip/HIPContext.h>
 #endif
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-
-using bf16 = __hip_bfloat16;
+#include "ffn_tile.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int BM = 256;
-constexpr int K1 = 280;
-constexpr int K1P = 296;        // W1 row stride, bias col 287
-constexpr int NC = 64;
-constexpr int NHID = 2048;
-constexpr int NCHUNK = NHID / NC;
-constexpr int W2_STRIDE = 72;   // 9 granules/row; granule 8 is a pad slot
-constexpr int W2_ROWS = 288;    // staged rows (outputs 0..279 + 8 pad)
-constexpr int NOUT = 280;
-
-constexpr int W1_ELEMS = NC * K1P;          // 18,944 elems / buffer
-constexpr int W2_ELEMS = W2_ROWS * W2_STRIDE;  // 20,736 elems / buffer
-constexpr int W1_CHUNKS = W1_ELEMS * 2 / 1024;  // 37 KiB -> 5 issues/wave
-constexpr int W2_GRAN = W2_ROWS * 9;        // 2,592 granules
-constexpr int W2_CHUNKS = (W2_GRAN + 63) / 64;  // 41 -> 6 issues/wave
-
-constexpr int OFF_W1 = 0;                       // elems; [2] buffers
-constexpr int OFF_W2 = 2 * W1_ELEMS;            // 37,888
-constexpr int OFF_SCRATCH = OFF_W2 + 2 * W2_ELEMS;  // 79,360
-constexpr int LDS_ELEMS = OFF_SCRATCH + 1024;   // 160,768 B total
 
 // Epilogue transpose slices: one eighth of W1[1] and of W2[1] per wave,
 // each holding 4 fp32 output rows (4 x 1,120 B).
@@ -70,29 +46,6 @@ static_assert(EPI_A * 2 >= 4 * NOUT * 4 && EPI_B * 2 >= 4 * NOUT * 4,
               "a slice holds 4 fp32 rows");
 static_assert((EPI_A * 2) % 16 == 0 && (EPI_B * 2) % 16 == 0,
               "slices stay 16-B aligned");
-
-__device__ __forceinline__ void glds16(const bf16* gsrc, bf16* ldst) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) unsigned*)gsrc,
-      (__attribute__((address_space(3))) unsigned*)ldst, 16, 0, 0);
-}
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-// Un-hoistable lane id (see fused_ffn_v3.hip): nothing lane-derived may
-// live across the chunk loop at the 256-VGPR wall.
-__device__ __forceinline__ int lane_recompute() {
-  int l;
-  asm volatile(
-      "v_mbcnt_lo_u32_b32 %0, -1, 0\n\t"
-      "v_mbcnt_hi_u32_b32 %0, -1, %0"
-      : "=v"(l));
-  return l;
-}
 
 __device__ __forceinline__ float bf16_lo(unsigned w) {
   return __uint_as_float(w << 16);
@@ -114,43 +67,10 @@ __global__ __launch_bounds__(512, 1) void fused_ffn_v5_kernel(
   // wave id lives in an SGPR (readfirstlane) — free to keep live.
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
-  // ---- glds issue helpers, as in v3: wave-uniform 1-KiB LDS chunks,
-  // per-lane global sources, out-of-range chunks exec-masked off, lane id
-  // re-derived per call and the LDS destination pinned to an SGPR. ----
-  auto issue_w1 = [&](int chunk, int buf) {
-    const int ln = lane_recompute();
-    const bf16* src = w1 + (size_t)chunk * W1_ELEMS;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      const int ck = wave + i * 8;
-      if (ck < W1_CHUNKS) {
-        const int dst_off = __builtin_amdgcn_readfirstlane(
-            OFF_W1 + buf * W1_ELEMS + ck * 512);
-        glds16(src + ck * 512 + ln * 8, &smem[dst_off]);
-      }
-    }
-  };
-  auto issue_w2 = [&](int chunk, int buf) {
-    const int ln = lane_recompute();
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const int ck = wave + i * 8;
-      const int g = ck * 64 + ln;
-      if (g < W2_GRAN) {
-        const int row = g / 9, sub = g % 9;
-        const int k8 = sub == 8 ? 0 : sub;  // pad slot re-loads granule 0
-        const int dst_off = __builtin_amdgcn_readfirstlane(
-            OFF_W2 + buf * W2_ELEMS + ck * 512);
-        glds16(w2 + (size_t)row * NHID + chunk * NC + 8 * k8,
-               &smem[dst_off]);
-      }
-    }
-  };
-
   // The only cold chunk 0 of this block; every later tile finds its
   // chunk 0 issued during the previous tile's last chunk.
-  issue_w1(0, 0);
-  issue_w2(0, 0);
+  issue_w1(smem, w1, wave, 0, 0);
+  issue_w2(smem, w2, wave, 0, 0);
 
   for (int tile = blockIdx.x; tile < num_tiles; tile += gridDim.x) {
     const int m0 = tile * BM;
@@ -208,58 +128,23 @@ __global__ __launch_bounds__(512, 1) void fused_ffn_v5_kernel(
       // issues the next tile's chunk 0 into buffer 0 (= buf ^ 1).
       const int nxt = (chunk + 1) & (NCHUNK - 1);
       if (chunk + 1 < NCHUNK || has_next) {
-        issue_w1(nxt, buf ^ 1);
-        issue_w2(nxt, buf ^ 1);
+        issue_w1(smem, w1, wave, nxt, buf ^ 1);
+        issue_w2(smem, w2, wave, nxt, buf ^ 1);
       }
       const bf16* w1buf = &smem[OFF_W1 + buf * W1_ELEMS];
       const bf16* w2buf = &smem[OFF_W2 + buf * W2_ELEMS];
 
-      // ---- Per 32-hidden tile: swapped B1 (hidden in regs, m in lanes),
-      // ReLU, T12 repack to pa[2], then its two B2 k-steps (v3's loop
-      // body verbatim). ----
+      // Per 32-hidden tile: B1, ReLU, repack, then its two B2 k-steps —
+      // v3's sequence of the shared steps.
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        f32x16 acc = {};
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int s = 0; s < 18; ++s) {
-          const bf16x8 wfr = *reinterpret_cast<const bf16x8*>(
-              &w1buf[(32 * t + c) * K1P + 16 * s + 8 * hi]);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfr, af[s], acc,
-                                                        0, 0, 0);
-        }
-        __builtin_amdgcn_s_setprio(0);
-        float st[16];
+        const f32x16 acc = b1_step(w1buf, af, t, c, hi);
+        f32x16 st;
 #pragma unroll
         for (int r = 0; r < 16; ++r) st[r] = acc[r] > 0.f ? acc[r] : 0.f;
         bf16x8 pa[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const unsigned x0 = cvt_pk_bf16(st[8 * s + 0], st[8 * s + 1]);
-          const unsigned y0 = cvt_pk_bf16(st[8 * s + 2], st[8 * s + 3]);
-          const unsigned x1 = cvt_pk_bf16(st[8 * s + 4], st[8 * s + 5]);
-          const unsigned y1 = cvt_pk_bf16(st[8 * s + 6], st[8 * s + 7]);
-          const auto rx = __builtin_amdgcn_permlane32_swap(x0, x1, false,
-                                                           false);
-          const auto ry = __builtin_amdgcn_permlane32_swap(y0, y1, false,
-                                                           false);
-          unsigned u[4] = {(unsigned)rx[0], (unsigned)ry[0],
-                           (unsigned)rx[1], (unsigned)ry[1]};
-          pa[s] = *reinterpret_cast<const bf16x8*>(u);
-        }
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-#pragma unroll
-          for (int ct = 0; ct < 9; ++ct) {
-            const int ocol = min(32 * ct + c, NOUT - 1);
-            const bf16x8 wfr = *reinterpret_cast<const bf16x8*>(
-                &w2buf[ocol * W2_STRIDE + 32 * t + 16 * s + 8 * hi]);
-            oacc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                pa[s], wfr, oacc[ct], 0, 0, 0);
-          }
-        }
-        __builtin_amdgcn_s_setprio(0);
+        t12_repack(st, pa);
+        b2_step(w2buf, pa, oacc, t, c, hi);
       }
 
       // The DMA groups issued above must have landed and every wave must

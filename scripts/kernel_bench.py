@@ -60,6 +60,10 @@ def main():
                      args.iters)
         print(f"fused_ffn_v3 M={M}: {us4:.1f} us "
               f"({flops / us4 / 1e6:.0f} GF/s)")
+        us5 = timeit(lambda: ext.fused_ffn_v5(x, w1v2, w2, b2, 0.5, 0),
+                     args.iters)
+        print(f"fused_ffn_v5 M={M}: {us5:.1f} us "
+              f"({flops / us5 / 1e6:.0f} GF/s)")
         # hipBLASLt pair for comparison.
         w1t = torch.randn(280, 2048, device="cuda").to(torch.bfloat16)
         w2t = torch.randn(2048, 280, device="cuda").to(torch.bfloat16)

@@ -71,6 +71,17 @@ def test_v5_bitwise_equals_v3(ext, weights, M, max_blocks):
     )
 
 
+def test_ablate_mode0_bitwise_equals_v3(ext, weights):
+    """ffn_ablate mode 0 is v3's sequencing of the shared tile core."""
+    w1, w2, b2 = weights
+    x = _x(257, 1257)
+    ref = ext.fused_ffn_v3(x, w1, w2, b2, ALPHA)
+    out = ext.ffn_ablate(x, w1, w2, b2, ALPHA, 0)
+    torch.cuda.synchronize()
+    assert out.shape == ref.shape
+    assert torch.equal(out.view(torch.int16), ref.view(torch.int16))
+
+
 def test_v5_deterministic_across_runs(ext, weights):
     """Races in this kernel family showed up as schedule-dependent NaNs."""
     w1, w2, b2 = weights
