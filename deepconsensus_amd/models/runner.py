@@ -2,7 +2,9 @@
 
 MI355X-native execution of the reference's run_model_on_examples
 (quick_inference.py:341-415): on GPU the path is
-  embed_gather (HIP, K2) -> condenser GEMM (hipBLASLt, K3)
+  fused_embed_condense (HIP, K2+K3+K4: embedding gather inside the
+  condenser GEMM + position add; DC_FUSED_EMBED=0 runs embed_gather (K2)
+  -> fused_condense (K3+K4) instead, DC_FUSED_CONDENSE=0 the hipBLASLt GEMM)
   -> per layer: fused-QKV GEMM -> banded_attn (HIP, K5-K7) -> out-proj GEMM
      -> ReZero add -> FFN GEMMs (bias fused) -> ReZero add, all bf16
   -> fused_ln_head_qv (HIP, K10+K11+K12) emitting uint8 base ids + QVs.
@@ -256,6 +258,10 @@ class InferenceRunner:
                 self.pos_f32 = (
                     model.pos_encoding.detach().float().contiguous().to(dev)
                 )
+        # fused_embed_condense (K2+K3+K4) gathers the embeddings inside
+        # the condenser whenever the fused condenser is on; DC_FUSED_EMBED=0
+        # restores embed_gather + fused_condense (bitwise-equal output).
+        self.fused_embed = _os.environ.get("DC_FUSED_EMBED") != "0"
         # Packed per-layer weights (fast rezero path); generic fallback keeps
         # a bf16 deepcopy of the layer stack for non-rezero configs.
         self.rezero_fast = all(
@@ -387,25 +393,37 @@ class InferenceRunner:
     @torch.no_grad()
     def encode_native(self, rows: torch.Tensor) -> torch.Tensor:
         """Native path up to (but excluding) the final LayerNorm: [B,L,H] bf16."""
-        with trace.range("K2_embed_gather"):
-            emb = self.ext.embed_gather(
-                rows.contiguous(), self.table_flat, self.row_shift,
-                self.row_vocab, self.chunk_cnt, self.chunk_entries,
-            )  # [B, L, concat] bf16
-        b, l, _ = emb.shape
+        rows = rows.contiguous()
+        b, _, l = rows.shape
+        gather_args = (
+            rows, self.table_flat, self.row_shift, self.row_vocab,
+            self.chunk_cnt, self.chunk_entries,
+        )
         if self.cond_img is not None:
-            with trace.range("K3_condenser"):
-                h = self.cond_wt.shape[1]
-                pos = (
-                    self.pos_f32
-                    if self.pos_f32 is not None
-                    else emb.new_empty(0, dtype=torch.float32)
-                )
-                x = self.ext.fused_condense(
-                    emb.reshape(b * l, -1), self.cond_img, pos, h, l
-                )
+            h = self.cond_wt.shape[1]
+            pos = (
+                self.pos_f32
+                if self.pos_f32 is not None
+                else torch.empty(0, dtype=torch.float32, device=rows.device)
+            )
+            if self.fused_embed:
+                # K2+K3+K4 in one kernel: the condenser gathers its A
+                # fragments from the tables; [B, L, concat] never exists.
+                with trace.range("K2_K3_embed_condense"):
+                    x = self.ext.fused_embed_condense(
+                        *gather_args, self.cond_img, pos, h
+                    )
+            else:
+                with trace.range("K2_embed_gather"):
+                    emb = self.ext.embed_gather(*gather_args)
+                with trace.range("K3_condenser"):
+                    x = self.ext.fused_condense(
+                        emb.reshape(b * l, -1), self.cond_img, pos, h, l
+                    )
             x = x.view(b, l, -1)
         else:
+            with trace.range("K2_embed_gather"):
+                emb = self.ext.embed_gather(*gather_args)  # [B, L, concat]
             with trace.range("K3_condenser"):
                 x = emb.reshape(b * l, -1) @ self.cond_wt  # [B*L, H]
             x = x.view(b, l, -1)

@@ -35,9 +35,17 @@ using bf16 = __hip_bfloat16;
 //
 // One 64-lane wave per position: lanes split the H dims, shuffle-reduce the
 // mean/var and the 5 head dots, lane 0 finishes softmax+QV.
+//
+// Lane `lane` owns dims d = lane + 64*j, j < NS (NS = slots covering H).
+// Its gamma, beta and five w_head values do not change from row to row:
+// they are loaded once, before the persistent loop, into registers (7 per
+// slot), so a row costs NS x loads only. The next row's x loads are issued
+// before the current row's reductions and lane-0 tail. The arithmetic (the
+// per-lane sums in slot order, the xor-shuffle trees, the tail) is the
+// wave-per-position kernel's, expression for expression.
 namespace {
 
-template <typename T>
+template <typename T, int NS = 8>
 __global__ __launch_bounds__(256) void fused_ln_head_qv_kernel(
     const T* __restrict__ x, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ w_head,
@@ -47,21 +55,57 @@ __global__ __launch_bounds__(256) void fused_ln_head_qv_kernel(
     float max_qual) {
   const int wave_in_block = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
+
+  float g[NS], bt[NS], wh[5][NS];
+#pragma unroll
+  for (int j = 0; j < NS; ++j) {
+    const int d = lane + 64 * j;
+    g[j] = 0.f;
+    bt[j] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) wh[k][j] = 0.f;
+    if (d < H) {
+      g[j] = gamma[d];
+      bt[j] = beta[d];
+#pragma unroll
+      for (int k = 0; k < 5; ++k) wh[k][j] = w_head[k * H + d];
+    }
+  }
+
   // Persistent waves: one-shot wave-per-position launched N/4 tiny blocks
   // and was launch/drain-bound (~11x the HBM time at N=409600).
-  for (int n = blockIdx.x * 4 + wave_in_block; n < N; n += gridDim.x * 4) {
-  const T* xi = x + (size_t)n * H;
-
+  const int stride = gridDim.x * 4;
+  int n = blockIdx.x * 4 + wave_in_block;
+  T xr[NS];  // raw row, loaded one trip ahead
+  if (n < N) {
+    const T* xi = x + (size_t)n * H;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      const int d = lane + 64 * j;
+      if (d < H) xr[j] = xi[d];
+    }
+  }
+  for (; n < N; n += stride) {
   // Per-lane partial sums over dims lane, lane+64, ...
   float sum = 0.f;
-  float xv[8];  // H <= 512 supported
-  int nd = 0;
-  for (int d = lane; d < H; d += 64, ++nd) {
-    float v;
-    if constexpr (std::is_same_v<T, bf16>) v = __bfloat162float(xi[d]);
-    else v = xi[d];
-    xv[nd] = v;
-    sum += v;
+  float xv[NS];
+#pragma unroll
+  for (int j = 0; j < NS; ++j) {
+    if (lane + 64 * j < H) {
+      float v;
+      if constexpr (std::is_same_v<T, bf16>) v = __bfloat162float(xr[j]);
+      else v = xr[j];
+      xv[j] = v;
+      sum += v;
+    }
+  }
+  if (n + stride < N) {
+    const T* xi = x + (size_t)(n + stride) * H;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      const int d = lane + 64 * j;
+      if (d < H) xr[j] = xi[d];
+    }
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
@@ -70,10 +114,12 @@ __global__ __launch_bounds__(256) void fused_ln_head_qv_kernel(
   // sumsq/H - mean^2 cancels catastrophically on near-constant rows
   // (offset >> spread) and can go negative, making rstd NaN.
   float sq = 0.f;
-  nd = 0;
-  for (int d = lane; d < H; d += 64, ++nd) {
-    const float dv = xv[nd] - mean;
-    sq += dv * dv;
+#pragma unroll
+  for (int j = 0; j < NS; ++j) {
+    if (lane + 64 * j < H) {
+      const float dv = xv[j] - mean;
+      sq += dv * dv;
+    }
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off, 64);
@@ -84,11 +130,13 @@ __global__ __launch_bounds__(256) void fused_ln_head_qv_kernel(
   float logit[5];
 #pragma unroll
   for (int k = 0; k < 5; ++k) logit[k] = 0.f;
-  nd = 0;
-  for (int d = lane; d < H; d += 64, ++nd) {
-    const float normed = (xv[nd] - mean) * rstd * gamma[d] + beta[d];
 #pragma unroll
-    for (int k = 0; k < 5; ++k) logit[k] += normed * w_head[k * H + d];
+  for (int j = 0; j < NS; ++j) {
+    if (lane + 64 * j < H) {
+      const float normed = (xv[j] - mean) * rstd * g[j] + bt[j];
+#pragma unroll
+      for (int k = 0; k < 5; ++k) logit[k] += normed * wh[k][j];
+    }
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -159,23 +207,27 @@ std::vector<at::Tensor> fused_ln_head_qv(
   hipStream_t stream = at::hip::getCurrentHIPStream();
   auto gc = gamma.contiguous(), bc = beta.contiguous();
   auto wc = w_head.contiguous(), bhc = b_head.contiguous();
+  // Register slots per lane: 2, 5 (H = 280) or 8 cover every H <= 512.
+  auto launch = [&](auto tag) {
+    using T = decltype(tag);
+    auto go = [&](auto kern) {
+      hipLaunchKernelGGL(kern, grid, block, 0, stream,
+                         reinterpret_cast<const T*>(xc.data_ptr()),
+                         gc.data_ptr<float>(), bc.data_ptr<float>(),
+                         wc.data_ptr<float>(), bhc.data_ptr<float>(),
+                         bases.data_ptr<uint8_t>(), quals.data_ptr<uint8_t>(),
+                         probs_ptr, N, H, (float)cal_threshold, (float)cal_w,
+                         (float)cal_b, (float)max_qual);
+    };
+    if (H <= 128) go(fused_ln_head_qv_kernel<T, 2>);
+    else if (H <= 320) go(fused_ln_head_qv_kernel<T, 5>);
+    else go(fused_ln_head_qv_kernel<T, 8>);
+  };
   if (xc.dtype() == at::kBFloat16) {
-    hipLaunchKernelGGL(fused_ln_head_qv_kernel<bf16>, grid, block, 0, stream,
-                       reinterpret_cast<bf16*>(xc.data_ptr()),
-                       gc.data_ptr<float>(), bc.data_ptr<float>(),
-                       wc.data_ptr<float>(), bhc.data_ptr<float>(),
-                       bases.data_ptr<uint8_t>(), quals.data_ptr<uint8_t>(),
-                       probs_ptr, N, H, (float)cal_threshold, (float)cal_w,
-                       (float)cal_b, (float)max_qual);
+    launch(bf16{});
   } else {
     DC_CHECK(xc.dtype() == at::kFloat, "x must be bf16 or fp32");
-    hipLaunchKernelGGL(fused_ln_head_qv_kernel<float>, grid, block, 0, stream,
-                       xc.data_ptr<float>(), gc.data_ptr<float>(),
-                       bc.data_ptr<float>(), wc.data_ptr<float>(),
-                       bhc.data_ptr<float>(), bases.data_ptr<uint8_t>(),
-                       quals.data_ptr<uint8_t>(), probs_ptr, N, H,
-                       (float)cal_threshold, (float)cal_w, (float)cal_b,
-                       (float)max_qual);
+    launch(float{});
   }
   if (want_probs) return {bases, quals, probs};
   return {bases, quals};
@@ -235,6 +287,11 @@ at::Tensor banded_attn_bwd_mfma(
     int64_t H, int64_t win, double p_drop);
 at::Tensor fused_condense(at::Tensor x, at::Tensor w, at::Tensor pos,
                           int64_t n_out, int64_t seq_len);
+at::Tensor fused_embed_condense(at::Tensor rows, at::Tensor table_flat,
+                                at::Tensor row_shift, at::Tensor row_vocab,
+                                at::Tensor chunk_cnt,
+                                at::Tensor chunk_entries, at::Tensor w,
+                                at::Tensor pos, int64_t n_out);
 std::vector<at::Tensor> ffn_train_fwd(at::Tensor x, at::Tensor w1,
                                       at::Tensor w2, at::Tensor b2,
                                       double p_drop, int64_t seed);
@@ -303,6 +360,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_condense", &fused_condense,
         "Condenser GEMM [M,560]x[560,N] + fused position-encoding add "
         "(K3+K4)");
+  m.def("fused_embed_condense", &fused_embed_condense,
+        "Embedding gather inside the condenser GEMM + position-encoding "
+        "add (K2+K3+K4): fused_condense(embed_gather(rows)) bit for bit");
   m.def("ffn_train_fwd", &ffn_train_fwd,
         "Training FFN forward: relu + hash dropout in-register, returns "
         "(y, hd)");
