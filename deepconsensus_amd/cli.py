@@ -104,6 +104,14 @@ def _run_main(argv: List[str]) -> None:
                     "unspaced reads, the GPU builds the planes; numpy on "
                     "CPU). device needs --featurize_mode device. Default: "
                     "the DC_SPACING_MODE environment variable, else host")
+    ap.add_argument("--expand_mode", default=None,
+                    choices=list(qi.EXPAND_MODES),
+                    help="alignment expansion of the subread records: host "
+                    "(workers decode and expand every record) or device "
+                    "(workers ship the packed sequence, pw / ip and an op "
+                    "table per record, the GPU expands them; numpy on CPU). "
+                    "device needs --spacing_mode device. Default: the "
+                    "DC_EXPAND_MODE environment variable, else host")
     ap.add_argument("--use_only_gpu_index", type=int, default=None,
                     help="pin inference to this GPU index "
                     "(shorthand for --device cuda:N)")
@@ -133,6 +141,7 @@ def _run_main(argv: List[str]) -> None:
         featurize_mode=args.featurize_mode,
         passthrough_mode=args.passthrough_mode,
         spacing_mode=args.spacing_mode,
+        expand_mode=args.expand_mode,
     )
     if args.shard:
         i, n = args.shard.split("/")

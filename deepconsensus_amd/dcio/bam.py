@@ -645,6 +645,52 @@ def raw_tag(buf: bytes, name: str, default: Any = None) -> Any:
     return default
 
 
+def raw_tag_views(buf: bytes, names: Sequence[str],
+                  off: Optional[int] = None) -> Dict[str, Tuple[str, Any]]:
+    """raw_tag for several tags in one scan, without copying: name ->
+    (type, value) for every tag of ``names`` the record has. A ``B`` array
+    comes back as (subtype letter, read-only view into ``buf``), any other
+    tag as (type letter, decoded value). ``off`` is the offset of the tag
+    block when the caller has it already."""
+    if off is None:
+        l_read_name = buf[8]
+        n_cigar = struct.unpack_from("<H", buf, 12)[0]
+        l_seq = struct.unpack_from("<l", buf, 16)[0]
+        off = 32 + l_read_name + 4 * n_cigar + (l_seq + 1) // 2 + l_seq
+    want = {name.encode(): name for name in names}
+    out: Dict[str, Tuple[str, Any]] = {}
+    n = len(buf)
+    while off + 3 <= n and len(out) < len(want):
+        name = want.get(buf[off:off + 2])
+        typ = chr(buf[off + 2])
+        off += 3
+        if typ == "A":
+            if name:
+                out[name] = (typ, chr(buf[off]))
+            off += 1
+        elif typ in _TAG_FMT:
+            fmt = _TAG_FMT[typ]
+            if name:
+                out[name] = (typ, struct.unpack_from("<" + fmt, buf, off)[0])
+            off += struct.calcsize(fmt)
+        elif typ in ("Z", "H"):
+            end = buf.index(0, off)
+            if name:
+                out[name] = (typ, buf[off:end].decode())
+            off = end + 1
+        elif typ == "B":
+            sub = chr(buf[off])
+            count = struct.unpack_from("<I", buf, off + 1)[0]
+            dt = _ARRAY_DTYPE[sub]
+            if name:
+                out[name] = (sub, np.frombuffer(
+                    buf, dtype=dt, count=count, offset=off + 5))
+            off += 5 + count * np.dtype(dt).itemsize
+        else:
+            raise ValueError(f"unknown tag type {typ!r}")
+    return out
+
+
 class RawBamReader:
     """Sequential reader yielding RAW record buffers (no record decode).
 

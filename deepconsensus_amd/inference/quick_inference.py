@@ -38,6 +38,7 @@ from deepconsensus_amd.postprocess import stitch as stitch_utils
 from deepconsensus_amd.postprocess import stitch_device
 from deepconsensus_amd.preprocess import featurize_device
 from deepconsensus_amd.preprocess import feeder as pre_feeder
+from deepconsensus_amd.preprocess import expand_device
 from deepconsensus_amd.preprocess import spacing_device
 from deepconsensus_amd.preprocess import windows as windows_lib
 from deepconsensus_amd.preprocess.windows import DcConfig
@@ -124,12 +125,20 @@ class InferenceOptions:
     # GPU instead of spacing every read in the worker. Only defined with
     # featurize_mode "device".
     spacing_mode: Optional[str] = None
+    # Alignment expansion of the subread records: "host" | "device". None
+    # reads DC_EXPAND_MODE (default "host"). "device" has the workers ship
+    # the records' packed sequence, pw / ip arrays and an op table
+    # (preprocess/expand_device.py) and expands them on the GPU instead of
+    # decoding and expanding every record in the worker. Only defined with
+    # spacing_mode "device".
+    expand_mode: Optional[str] = None
 
 
 STITCH_MODES = ("serial", "pool", "device")
 FEATURIZE_MODES = ("host", "device")
 PASSTHROUGH_MODES = ("host", "device")
 SPACING_MODES = ("host", "device")
+EXPAND_MODES = ("host", "device")
 
 
 def resolve_stitch_mode(options: InferenceOptions) -> str:
@@ -199,6 +208,26 @@ def resolve_spacing_mode(options: InferenceOptions) -> str:
     return mode
 
 
+def resolve_expand_mode(options: InferenceOptions) -> str:
+    """options.expand_mode if set, else the DC_EXPAND_MODE env knob.
+    "device" needs spacing mode "device"."""
+    mode = options.expand_mode
+    if mode is None:
+        mode = os.environ.get("DC_EXPAND_MODE", "host")
+    if mode not in EXPAND_MODES:
+        raise ValueError(
+            f"expand_mode must be one of {EXPAND_MODES}, got {mode!r}"
+        )
+    if mode == "device":
+        spacing = resolve_spacing_mode(options)
+        if spacing != "device":
+            raise ValueError(
+                f"expand_mode 'device' needs spacing_mode 'device', got "
+                f"spacing_mode {spacing!r}"
+            )
+    return mode
+
+
 @dataclasses.dataclass
 class ZmwWindows:
     """Worker output for one ZMW: model windows pre-stacked, skipped
@@ -226,7 +255,8 @@ class ZmwWindows:
     # "device": the planes also carry the skipped windows as a passthrough
     # table (``skipped`` is then empty), and stay when no window is
     # model-bound. spacing_mode "device": a spacing_device.ZmwUnspaced
-    # with the same tables stands here instead.
+    # with the same tables stands here instead; expand_mode "device": an
+    # expand_device.ZmwRaw.
     planes: Optional[featurize_device.ZmwPlanes] = None
 
     @property
@@ -255,6 +285,19 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
     expand_counter = None
     if isinstance(subreads, pre_feeder.ZmwJob):
         expand_counter = collections.Counter()
+        if (stage != DebugStage.DC_INPUT
+                and resolve_expand_mode(options) == "device"):
+            # No record is decoded or expanded here. None for a ZMW off
+            # this path: it is materialized below, as in expand_mode "host".
+            raw = expand_device.build_raw(
+                subreads, dc_config, window_widths, subreads.ins_trim,
+                expand_counter,
+            )
+            if raw is not None:
+                ccs, raw.ccs_read = raw.ccs_read, None
+                return _unspaced_zmw_windows(
+                    zmw, raw, ccs, options, expand_counter
+                )
         subreads = subreads.materialize(expand_counter)
     if (stage != DebugStage.DC_INPUT
             and resolve_spacing_mode(options) == "device"
@@ -630,6 +673,7 @@ class _ModelChunks:
     def _init_planes(self) -> None:
         if not self.native:
             self.batch = featurize_device.pack_batch(self.packed_zmws)
+            expand_device.expand_batch_numpy(self.batch)
             spacing_device.space_batch_numpy(self.batch)
         else:
             device = self.runner.device
@@ -679,7 +723,7 @@ class _ModelChunks:
                 view("pt_tab", batch.pt_tab).view(batch.pt_tab.shape),
             )
             if batch.spacing is not None:
-                self._space_on_device(view, staging[1])
+                self._space_on_device(view, staging[1:])
             if batch.fallback_rows is not None:
                 self.fallback_rows = torch.from_numpy(
                     batch.fallback_rows
@@ -690,17 +734,42 @@ class _ModelChunks:
         self.n_model = self.batch.n_windows
         self.row_length = self.batch.max_length
 
-    def _space_on_device(self, view, staged: torch.Tensor) -> None:
+    def _space_on_device(self, view, staged: List[torch.Tensor]) -> None:
         """Fills the device planes of the unspaced ZMWs: one copy of the
         packed reads, then the subread_space kernel, on the stream of the
         kernels that read the planes. ZMWs spaced on the host have their
-        planes copied into their slices."""
+        planes copied into their slices. With raw ZMWs (expand_mode
+        "device") ``src`` is allocated on the device, the host-written part
+        copied in, and the cigar_expand kernel fills the rest from the
+        expand blob ahead of subread_space."""
         batch, sp = self.batch, self.batch.spacing
-        sp_blob = staged.to(self.runner.device, non_blocking=True)
+        device = self.runner.device
+        sp_blob = staged[0].to(device, non_blocking=True)
 
         def sp_view(name: str, array: np.ndarray, dtype) -> torch.Tensor:
             lo = sp.offsets[name]
             return sp_blob[lo : lo + array.nbytes].view(dtype)
+
+        src = sp_view("src", sp.src, torch.uint8)
+        if sp.expand is not None:
+            ex = sp.expand
+            ex_blob = staged[1].to(device, non_blocking=True)
+
+            def ex_view(name: str, array: np.ndarray, dtype) -> torch.Tensor:
+                lo = ex.offsets[name]
+                return ex_blob[lo : lo + array.nbytes].view(dtype)
+
+            host_src = src
+            src = torch.empty(sp.n_src, dtype=torch.uint8, device=device)
+            src[: sp.n_src_host].copy_(host_src)
+            self.runner.ext.cigar_expand_into(
+                ex_view("raw", ex.raw, torch.uint8),
+                ex_view("op_tab", ex.op_tab, torch.int32).view(
+                    ex.op_tab.shape),
+                ex_view("xr_tab", ex.xr_tab, torch.int64).view(
+                    ex.xr_tab.shape),
+                src, torch.from_numpy(expand_device.NT16_LUT),
+            )
 
         sub, ccs, ccs_bq, zmw_tab = self.dev
         ccs_q = self.pt_dev[1]
@@ -710,7 +779,7 @@ class _ModelChunks:
                 torch.from_numpy(array))
         ins_max = sp_view("ins_max", sp.ins_max, torch.int16)
         self.runner.ext.subread_space_into(
-            sp_view("src", sp.src, torch.uint8), ins_max,
+            src, ins_max,
             sp_view("sp_tab", sp.sp_tab, torch.int64).view(sp.sp_tab.shape),
             sp_view("read_tab", sp.read_tab, torch.int64).view(
                 sp.read_tab.shape),
@@ -1142,6 +1211,7 @@ def run(
     resolve_featurize_mode(options)  # a bad value fails here, not in a worker
     resolve_passthrough_mode(options)  # so does a mode combination
     resolve_spacing_mode(options)
+    resolve_expand_mode(options)
     if resolve_stitch_mode(options) == "device":
         stitch_device.check_max_base_quality(options.max_base_quality)
 

@@ -336,8 +336,21 @@ void subread_space_into(at::Tensor src, at::Tensor ins_max,
                         at::Tensor sub, at::Tensor ccs, at::Tensor ccs_q,
                         at::Tensor ccs_bq, bool use_ccs_bq);
 int64_t subread_space_tile();
+// Defined in cigar_expand.hip.
+void cigar_expand_into(at::Tensor raw, at::Tensor op_tab, at::Tensor xr_tab,
+                       at::Tensor src, at::Tensor lut);
+int64_t cigar_expand_tile();
+int64_t cigar_expand_stage();
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("cigar_expand_into", &cigar_expand_into,
+        "Device alignment expansion: record operands + op tables -> the "
+        "unspaced reads (codes | pw | ip) in the caller-owned src of "
+        "subread_space_into; lut is the host uint8 [16] base-id table");
+  m.def("cigar_expand_tile", &cigar_expand_tile,
+        "Elements per tile of cigar_expand_into");
+  m.def("cigar_expand_stage", &cigar_expand_stage,
+        "Op rows per LDS stage of cigar_expand_into");
   m.def("subread_space_into", &subread_space_into,
         "Device subread spacing: unspaced reads + ins_max -> caller-owned "
         "zero-filled sub / ccs / ccs_q / ccs_bq planes");

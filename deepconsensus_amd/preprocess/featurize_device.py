@@ -324,7 +324,10 @@ def pack_batch(
     same table rows and the same, zero-filled, slices of the plane arrays,
     and its reads are packed into ``FeaturizeBatch.spacing`` (a second
     ``alloc`` call). ``device_planes`` then leaves the plane arrays out of
-    the host buffer (see FeaturizeBatch).
+    the host buffer (see FeaturizeBatch). An expand_device.ZmwRaw packs
+    like a ZmwUnspaced; its records go to ``FeaturizeBatch.spacing.expand``
+    (a third ``alloc`` call) and with ``device_planes`` its reads have no
+    host bytes at all.
 
     Raises ValueError when a table entry would make the kernel read
     outside a plane or when the ZMWs disagree on the layout.
@@ -520,7 +523,8 @@ def pack_batch(
         from deepconsensus_amd.preprocess import spacing_device
 
         spacing = spacing_device.pack_spacing(
-            unspaced_zmws, zmw_tab, sub_off, ccs_off, alloc=alloc)
+            unspaced_zmws, zmw_tab, sub_off, ccs_off, alloc=alloc,
+            device_src=device_planes)
     if n_windows:
         win_tab[:n_windows] = np.concatenate(win_parts)
     win_tab[n_windows:, 0] = -1

@@ -269,6 +269,15 @@ class SpacingBatch:
     read_tab: np.ndarray
     ins_max: np.ndarray
     src: np.ndarray
+    # expand_mode "device": the reads of expand_device.ZmwRaw items are not
+    # packed; their 3 * n_elem bytes are reserved behind the ``n_src_host``
+    # bytes the host wrote, and ``expand`` (expand_device.ExpandBatch) holds
+    # what the cigar_expand kernel or its twin fills them from. ``n_src`` is
+    # the whole length; with ``device_src`` the host ``src`` ends at
+    # n_src_host and the caller allocates the rest on the device.
+    n_src: int = 0
+    n_src_host: int = 0
+    expand: Any = None
 
 
 def _check(cond: bool, message: str) -> None:
@@ -346,21 +355,34 @@ def validate_spacing_tables(
                "read source offset past the end")
 
 
+def _is_raw(u: Any) -> bool:
+    return bool(getattr(u, "raw_records", False))
+
+
 def pack_spacing(
-    items: Sequence[Tuple[int, ZmwUnspaced]],
+    items: Sequence[Tuple[int, Any]],
     zmw_tab: np.ndarray,
     n_sub_bytes: int,
     n_ccs: int,
     alloc: Optional[Callable[[int], np.ndarray]] = None,
+    device_src: bool = False,
 ) -> SpacingBatch:
-    """Packs ``items`` = (row in zmw_tab, ZmwUnspaced) back to back and
-    validates the tables. ``alloc`` as in pack_batch."""
+    """Packs ``items`` = (row in zmw_tab, ZmwUnspaced or
+    expand_device.ZmwRaw) back to back and validates the tables. ``alloc``
+    as in pack_batch. The reads of a ZmwRaw get their place in ``src``
+    behind everything the host writes (see SpacingBatch); ``device_src``
+    leaves that part out of the host buffer."""
     n_reads = sum(u.n_sub for _, u in items)
+    n_src_host = sum((0 if _is_raw(u) else len(u.src)) + 2 * u.Lc
+                     for _, u in items)
+    n_src = n_src_host + sum(
+        3 * int(np.sum(u.n_elem, dtype=np.int64))
+        for _, u in items if _is_raw(u))
     sizes = [
         ("sp_tab", np.int64, len(items) * SP_COLS),
         ("read_tab", np.int64, n_reads * RD_COLS),
         ("ins_max", np.uint16, sum(u.Lc + 1 for _, u in items)),
-        ("src", np.uint8, sum(len(u.src) + 2 * u.Lc for _, u in items)),
+        ("src", np.uint8, n_src_host if device_src else n_src),
     ]
     offsets, total = {}, 0
     for name, dtype, count in sizes:
@@ -378,24 +400,34 @@ def pack_spacing(
     sp_tab = views["sp_tab"].reshape(len(items), SP_COLS)
     read_tab = views["read_tab"].reshape(n_reads, RD_COLS)
     ins_all, src = views["ins_max"], views["src"]
+    src[n_src_host:] = 0  # until the expand twin fills it
     read0 = ins_off = src_off = 0
+    born_off = n_src_host
+    raw_items = []
     for s, (zi, u) in enumerate(items):
         Lc = u.Lc
-        _check(u.src.dtype == np.uint8 and u.ccs.dtype == np.uint8
-               and u.ccs_q.dtype == np.uint8, "sources must be uint8")
+        _check(u.ccs.dtype == np.uint8 and u.ccs_q.dtype == np.uint8
+               and (_is_raw(u) or u.src.dtype == np.uint8),
+               "sources must be uint8")
         _check(u.ccs_q.shape == (Lc,), "ccs_q must be [Lc]")
         _check(u.ins_max.dtype == np.uint16
                and u.ins_max.shape == (Lc + 1,),
                "ins_max must be uint16 [Lc + 1]")
         n_elem = np.asarray(u.n_elem, np.int64)
-        _check(len(u.src) == 3 * int(n_elem.sum()),
-               "src is not three bytes per element")
+        n_bytes = 3 * int(n_elem.sum())
         read_tab[read0 : read0 + u.n_sub, RD_SP] = s
-        read_tab[read0 : read0 + u.n_sub, RD_SRC] = (
-            src_off + 3 * (np.cumsum(n_elem) - n_elem))
         read_tab[read0 : read0 + u.n_sub, RD_N] = n_elem
-        src[src_off : src_off + len(u.src)] = u.src
-        src_off += len(u.src)
+        read_off = 3 * (np.cumsum(n_elem) - n_elem)
+        if _is_raw(u):
+            read_tab[read0 : read0 + u.n_sub, RD_SRC] = born_off + read_off
+            raw_items.append((u, born_off + read_off))
+            born_off += n_bytes
+        else:
+            _check(len(u.src) == n_bytes,
+                   "src is not three bytes per element")
+            read_tab[read0 : read0 + u.n_sub, RD_SRC] = src_off + read_off
+            src[src_off : src_off + n_bytes] = u.src
+            src_off += n_bytes
         sp_tab[s] = (zi, read0, u.n_sub, Lc, ins_off, src_off,
                      SP_WANT_Q if u.want_q else 0)
         src[src_off : src_off + Lc] = u.ccs
@@ -404,10 +436,17 @@ def pack_spacing(
         ins_all[ins_off : ins_off + Lc + 1] = u.ins_max
         ins_off += Lc + 1
         read0 += u.n_sub
-    validate_spacing_tables(sp_tab, read_tab, ins_all, len(src), zmw_tab,
+    validate_spacing_tables(sp_tab, read_tab, ins_all, n_src, zmw_tab,
                             n_sub_bytes, n_ccs)
+    expand = None
+    if raw_items:
+        from deepconsensus_amd.preprocess import expand_device
+
+        expand = expand_device.pack_expand(
+            raw_items, n_src, n_src_host, read_tab, alloc=alloc)
     return SpacingBatch(blob=blob, offsets=offsets, sp_tab=sp_tab,
-                        read_tab=read_tab, ins_max=ins_all, src=src)
+                        read_tab=read_tab, ins_max=ins_all, src=src,
+                        n_src=n_src, n_src_host=n_src_host, expand=expand)
 
 
 def _load_zmw(sp_tab, zmw_tab, s, n_src, n_ins, n_sub_bytes, n_ccs):

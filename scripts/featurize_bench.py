@@ -18,6 +18,12 @@
   --spacing-kernel
              GPU: HIP-event time of subread_space_into on --zmws ZMWs next
              to a device-to-device copy_ of the bytes it writes.
+  --worker --spacing_mode device --expand_mode host|device
+             the same split for one expand_mode; under device the subreads'
+             share is build_raw.
+  --expand-kernel
+             GPU: HIP-event time of cigar_expand_into on --zmws ZMWs next to
+             a device-to-device copy_ of the bytes it writes.
 """
 import argparse
 import collections
@@ -108,6 +114,10 @@ def spacing_worker_main(args):
         "expand", pre_feeder.expand_clip_indent)
     pre_feeder.space_out_subreads = timed(
         "spacing+put_spacing", read_lib.space_out_subreads)
+    # expand_mode device: neither decode nor expand runs for the subreads;
+    # build_raw holds the record parse and the CCS decode.
+    qi.expand_device.build_raw = timed(
+        "build_raw", qi.expand_device.build_raw)
 
     with tempfile.TemporaryDirectory() as td:
         sub, ccs, _ = make_synth_bams(
@@ -116,6 +126,7 @@ def spacing_worker_main(args):
         options = qi.InferenceOptions(
             featurize_mode="device", stitch_mode="device",
             passthrough_mode=args.passthrough_mode, spacing_mode=mode,
+            expand_mode=args.expand_mode,
             skip_windows_above=args.skip_windows_above)
         for p in range(args.passes):
             proc_feeder, _ = pre_feeder.create_proc_feeder(
@@ -135,10 +146,12 @@ def spacing_worker_main(args):
                               for k, v in sorted(split.items()))
             unspaced = sum(getattr(z.planes, "unspaced", False)
                            for z in outs)
-            print(f"spacing={mode:6s} pass {p}: {1e3 * work_s / n:7.2f} "
+            raw = sum(getattr(z.planes, "raw_records", False) for z in outs)
+            print(f"spacing={mode:6s} expand={args.expand_mode or 'host':6s} "
+                  f"pass {p}: {1e3 * work_s / n:7.2f} "
                   f"ms/ZMW worker [{parts}, rest {1e3 * rest / n:.2f}], "
                   f"{sum(map(len, blobs)) / n / 1e3:8.1f} kB pickled/ZMW, "
-                  f"{unspaced}/{n} ZMWs unspaced")
+                  f"{unspaced}/{n} ZMWs unspaced, {raw} of them raw")
 
 
 def spacing_kernel_main(args):
@@ -208,6 +221,78 @@ def spacing_kernel_main(args):
         v = sorted(t[name])
         print(f"  {label:34s} median {statistics.median(v):8.1f} us  "
               f"min {v[0]:8.1f}  max {v[-1]:8.1f}")
+
+
+def expand_kernel_main(args):
+    """cigar_expand_into on a packed batch of --zmws raw ZMWs next to a
+    device-to-device copy_ of the bytes it writes."""
+    import torch
+
+    from deepconsensus_amd import ops
+    from deepconsensus_amd.inference import quick_inference as qi
+    from deepconsensus_amd.preprocess import expand_device as xd
+    from deepconsensus_amd.preprocess import featurize_device as fd
+    from deepconsensus_amd.preprocess import feeder as pre_feeder
+    from deepconsensus_amd.preprocess.windows import DcConfig
+    from deepconsensus_amd.utils.synth import make_synth_bams
+
+    ext = ops.get_ext(required=True)
+    with tempfile.TemporaryDirectory() as td:
+        sub, ccs, _ = make_synth_bams(
+            td, args.zmws, args.length, args.subreads, 3)
+        dc_config = DcConfig(20, 100, False)
+        options = qi.InferenceOptions(
+            featurize_mode="device", stitch_mode="device",
+            spacing_mode="device", expand_mode="device",
+            skip_windows_above=0)
+        proc_feeder, _ = pre_feeder.create_proc_feeder(
+            subreads_to_ccs=sub, ccs_bam=ccs, dc_config=dc_config,
+            defer_expansion=True)
+        outs = [qi.preprocess_one_zmw((zmw, subreads, dcc, ww, options))
+                for subreads, zmw, dcc, _, ww in proc_feeder()]
+    sp = fd.pack_batch(outs).spacing
+    ex = sp.expand
+    if ex is None:
+        raise SystemExit("no ZMW took the expand path")
+    dev = [torch.from_numpy(a.copy()).cuda()
+           for a in (ex.raw, ex.op_tab, ex.xr_tab)]
+    src = torch.zeros(sp.n_src, dtype=torch.uint8, device="cuda")
+    lut = torch.from_numpy(xd.NT16_LUT.copy())
+    n_written = 3 * int(ex.xr_tab[:, xd.XR_N].sum())
+    src_copy = torch.randint(0, 255, (n_written,), dtype=torch.uint8,
+                             device="cuda")
+    dst_copy = torch.empty_like(src_copy)
+
+    def timed(fn):
+        a, b = torch.cuda.Event(True), torch.cuda.Event(True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e3
+
+    run = lambda: ext.cigar_expand_into(*dev, src, lut)  # noqa: E731
+    copy = lambda: dst_copy.copy_(src_copy)  # noqa: E731
+    for _ in range(args.warmup):
+        run()
+        copy()
+    torch.cuda.synchronize()
+    t = {"kernel": [], "copy": []}
+    for _ in range(args.repeats):  # alternating, one process
+        t["kernel"].append(timed(run))
+        t["copy"].append(timed(copy))
+    print(f"{len(outs)} ZMWs x {args.subreads} subreads x {args.length} bp:"
+          f" {len(ex.xr_tab)} reads, {len(ex.op_tab)} op rows, "
+          f"{len(ex.raw) / 1e6:.2f} MB operands -> {n_written / 1e6:.2f} MB "
+          f"written; {args.repeats} launches each after {args.warmup} "
+          f"warm-up")
+    for name, label in (("kernel", "cigar_expand_into"),
+                        ("copy", "copy_ of the bytes written")):
+        v = sorted(t[name])
+        med = statistics.median(v)
+        print(f"  {label:28s} median {med:8.1f} us  min {v[0]:8.1f}  "
+              f"max {v[-1]:8.1f}  = {n_written / med / 1e3:7.1f} GB/s "
+              f"written")
 
 
 def kernel_main(args):
@@ -344,6 +429,13 @@ def main():
     ap.add_argument("--spacing-kernel", action="store_true",
                     help="GPU: subread_space_into on --zmws ZMWs next to "
                     "a copy_ of the plane bytes")
+    ap.add_argument("--expand_mode", default=None,
+                    choices=["host", "device"],
+                    help="with --worker --spacing_mode device: the worker "
+                    "cost under this expand_mode")
+    ap.add_argument("--expand-kernel", action="store_true",
+                    help="GPU: cigar_expand_into on --zmws ZMWs next to a "
+                    "copy_ of the bytes it writes")
     ap.add_argument("--passthrough_mode", default="host",
                     choices=["host", "device"])
     ap.add_argument("--passes", type=int, default=3)
@@ -360,6 +452,9 @@ def main():
         return
     if args.spacing_kernel:
         spacing_kernel_main(args)
+        return
+    if args.expand_kernel:
+        expand_kernel_main(args)
         return
     if args.worker:
         worker_main(args)

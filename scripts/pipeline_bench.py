@@ -41,6 +41,7 @@ def main():
     ap.add_argument("--featurize_mode", default=None)
     ap.add_argument("--passthrough_mode", default=None)
     ap.add_argument("--spacing_mode", default=None)
+    ap.add_argument("--expand_mode", default=None)
     args = ap.parse_args()
 
     import torch
@@ -76,6 +77,7 @@ def main():
             featurize_mode=args.featurize_mode,
             passthrough_mode=args.passthrough_mode,
             spacing_mode=args.spacing_mode,
+            expand_mode=args.expand_mode,
         )
         t0 = time.perf_counter()
         counter = qi.run(subreads_to_ccs=sub, ccs_bam=ccs,
@@ -94,7 +96,8 @@ def main():
               f"passthrough), modes: stitch={qi.resolve_stitch_mode(options)}"
               f" featurize={qi.resolve_featurize_mode(options)} "
               f"passthrough={qi.resolve_passthrough_mode(options)} "
-              f"spacing={qi.resolve_spacing_mode(options)}")
+              f"spacing={qi.resolve_spacing_mode(options)} "
+              f"expand={qi.resolve_expand_mode(options)}")
         # Per-stage main-thread time (preprocess overlaps via the prefetch
         # thread, so its visible share should be ~0 when pipelining works).
         stage_s = {}
