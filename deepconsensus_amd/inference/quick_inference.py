@@ -19,17 +19,19 @@ import collections
 import concurrent.futures
 import dataclasses
 import enum
+import functools
 import itertools
 import json
 import logging
 import os
 import time
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
 
 from deepconsensus_amd.calibration import calibration as calibration_lib
+from deepconsensus_amd.inference import model_chunks as model_chunks_lib
 from deepconsensus_amd.models import checkpoint as ckpt_lib
 from deepconsensus_amd.models import config as cfg
 from deepconsensus_amd.models.model import get_model
@@ -140,92 +142,61 @@ PASSTHROUGH_MODES = ("host", "device")
 SPACING_MODES = ("host", "device")
 EXPAND_MODES = ("host", "device")
 
+# The device stages: InferenceOptions field -> (environment knob read when
+# the field is None, choices, default, modes that must be "device" for this
+# one to be "device"). In the order `run` reports a bad value.
+MODE_TABLE = {
+    "featurize_mode": ("DC_FEATURIZE_MODE", FEATURIZE_MODES, "host", ()),
+    "passthrough_mode": ("DC_PASSTHROUGH_MODE", PASSTHROUGH_MODES, "host",
+                         ("featurize_mode", "stitch_mode")),
+    "spacing_mode": ("DC_SPACING_MODE", SPACING_MODES, "host",
+                     ("featurize_mode",)),
+    "expand_mode": ("DC_EXPAND_MODE", EXPAND_MODES, "host",
+                    ("spacing_mode",)),
+    "stitch_mode": ("DC_STITCH_MODE", STITCH_MODES, "serial", ()),
+}
 
-def resolve_stitch_mode(options: InferenceOptions) -> str:
-    """options.stitch_mode if set, else the DC_STITCH_MODE env knob."""
-    if options.stitch_mode is None:
-        return os.environ.get("DC_STITCH_MODE", "serial")
-    if options.stitch_mode not in STITCH_MODES:
-        raise ValueError(
-            f"stitch_mode must be one of {STITCH_MODES}, got "
-            f"{options.stitch_mode!r}"
-        )
-    return options.stitch_mode
+
+class Modes(NamedTuple):
+    """The five modes of a run, resolved and checked."""
+
+    featurize_mode: str
+    passthrough_mode: str
+    spacing_mode: str
+    expand_mode: str
+    stitch_mode: str
 
 
-def resolve_featurize_mode(options: InferenceOptions) -> str:
-    """options.featurize_mode if set, else the DC_FEATURIZE_MODE env knob."""
-    mode = options.featurize_mode
+def _resolve_mode(options: InferenceOptions, field: str) -> str:
+    """The option if set, else the environment knob, else the default; a
+    value outside the choices or a "device" without its prerequisites is a
+    ValueError."""
+    knob, choices, default, requires = MODE_TABLE[field]
+    mode = getattr(options, field)
     if mode is None:
-        mode = os.environ.get("DC_FEATURIZE_MODE", "host")
-    if mode not in FEATURIZE_MODES:
-        raise ValueError(
-            f"featurize_mode must be one of {FEATURIZE_MODES}, got {mode!r}"
-        )
+        mode = os.environ.get(knob, default)
+        if field == "stitch_mode":
+            return mode  # the knob's value has never been checked
+    if mode not in choices:
+        raise ValueError(f"{field} must be one of {choices}, got {mode!r}")
+    if mode == "device" and requires:
+        others = [_resolve_mode(options, r) for r in requires]
+        if others != ["device"] * len(requires):
+            needs = " and ".join(f"{r} 'device'" for r in requires)
+            got = " and ".join(
+                f"{r} {other!r}" for r, other in zip(requires, others))
+            raise ValueError(f"{field} 'device' needs {needs}, got {got}")
     return mode
 
 
-def resolve_passthrough_mode(options: InferenceOptions) -> str:
-    """options.passthrough_mode if set, else the DC_PASSTHROUGH_MODE env
-    knob. "device" needs featurize mode and stitch mode "device"."""
-    mode = options.passthrough_mode
-    if mode is None:
-        mode = os.environ.get("DC_PASSTHROUGH_MODE", "host")
-    if mode not in PASSTHROUGH_MODES:
-        raise ValueError(
-            f"passthrough_mode must be one of {PASSTHROUGH_MODES}, got "
-            f"{mode!r}"
-        )
-    if mode == "device":
-        others = (resolve_featurize_mode(options),
-                  resolve_stitch_mode(options))
-        if others != ("device", "device"):
-            raise ValueError(
-                f"passthrough_mode 'device' needs featurize_mode 'device' "
-                f"and stitch_mode 'device', got featurize_mode "
-                f"{others[0]!r} and stitch_mode {others[1]!r}"
-            )
-    return mode
+def resolve_modes(options: InferenceOptions) -> Modes:
+    return Modes(*(_resolve_mode(options, field) for field in MODE_TABLE))
 
 
-def resolve_spacing_mode(options: InferenceOptions) -> str:
-    """options.spacing_mode if set, else the DC_SPACING_MODE env knob.
-    "device" needs featurize mode "device"."""
-    mode = options.spacing_mode
-    if mode is None:
-        mode = os.environ.get("DC_SPACING_MODE", "host")
-    if mode not in SPACING_MODES:
-        raise ValueError(
-            f"spacing_mode must be one of {SPACING_MODES}, got {mode!r}"
-        )
-    if mode == "device":
-        featurize = resolve_featurize_mode(options)
-        if featurize != "device":
-            raise ValueError(
-                f"spacing_mode 'device' needs featurize_mode 'device', got "
-                f"featurize_mode {featurize!r}"
-            )
-    return mode
-
-
-def resolve_expand_mode(options: InferenceOptions) -> str:
-    """options.expand_mode if set, else the DC_EXPAND_MODE env knob.
-    "device" needs spacing mode "device"."""
-    mode = options.expand_mode
-    if mode is None:
-        mode = os.environ.get("DC_EXPAND_MODE", "host")
-    if mode not in EXPAND_MODES:
-        raise ValueError(
-            f"expand_mode must be one of {EXPAND_MODES}, got {mode!r}"
-        )
-    if mode == "device":
-        spacing = resolve_spacing_mode(options)
-        if spacing != "device":
-            raise ValueError(
-                f"expand_mode 'device' needs spacing_mode 'device', got "
-                f"spacing_mode {spacing!r}"
-            )
-    return mode
+# One resolver per mode, for callers that ask for a single one.
+(resolve_featurize_mode, resolve_passthrough_mode, resolve_spacing_mode,
+ resolve_expand_mode, resolve_stitch_mode) = (
+    functools.partial(_resolve_mode, field=field) for field in MODE_TABLE)
 
 
 @dataclasses.dataclass
@@ -250,14 +221,13 @@ class ZmwWindows:
     np_num_passes: Optional[int] = None
     rq: Optional[float] = None
     rg: Optional[str] = None
-    # featurize_mode "device": the model-bound windows as compact planes
-    # plus a window table; ``rows`` is then None. passthrough_mode
-    # "device": the planes also carry the skipped windows as a passthrough
-    # table (``skipped`` is then empty), and stay when no window is
-    # model-bound. spacing_mode "device": a spacing_device.ZmwUnspaced
-    # with the same tables stands here instead; expand_mode "device": an
-    # expand_device.ZmwRaw.
-    planes: Optional[featurize_device.ZmwPlanes] = None
+    # featurize_mode "device": the model-bound windows as a window table
+    # over compact planes (a ZmwPlanes); ``rows`` is then None.
+    # passthrough_mode "device": the tables also carry the skipped windows
+    # (``skipped`` is then empty), and stay when no window is model-bound.
+    # spacing_mode "device": over unspaced reads (a ZmwUnspaced);
+    # expand_mode "device": over undecoded records (a ZmwRaw).
+    planes: Optional[featurize_device.ZmwTables] = None
 
     @property
     def n_model(self) -> int:
@@ -282,11 +252,11 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
     """
     zmw, subreads, dc_config, window_widths, options = one_zmw
     stage = options.end_after_stage
+    modes = resolve_modes(options)
     expand_counter = None
     if isinstance(subreads, pre_feeder.ZmwJob):
         expand_counter = collections.Counter()
-        if (stage != DebugStage.DC_INPUT
-                and resolve_expand_mode(options) == "device"):
+        if stage != DebugStage.DC_INPUT and modes.expand_mode == "device":
             # No record is decoded or expanded here. None for a ZMW off
             # this path: it is materialized below, as in expand_mode "host".
             raw = expand_device.build_raw(
@@ -296,11 +266,10 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
             if raw is not None:
                 ccs, raw.ccs_read = raw.ccs_read, None
                 return _unspaced_zmw_windows(
-                    zmw, raw, ccs, options, expand_counter
+                    zmw, raw, ccs, options, modes, expand_counter
                 )
         subreads = subreads.materialize(expand_counter)
-    if (stage != DebugStage.DC_INPUT
-            and resolve_spacing_mode(options) == "device"
+    if (stage != DebugStage.DC_INPUT and modes.spacing_mode == "device"
             and isinstance(subreads, list)):
         # No read is spaced here. None for a ZMW off this path: it is
         # spaced below and ships planes, as in spacing_mode "host".
@@ -311,7 +280,7 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
         )
         if unspaced is not None:
             return _unspaced_zmw_windows(
-                zmw, unspaced, subreads[-1], options, expand_counter
+                zmw, unspaced, subreads[-1], options, modes, expand_counter
             )
         expand_counter = (expand_counter or collections.Counter())
         expand_counter.update(fallback_counter)
@@ -327,6 +296,28 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
         if expand_counter:
             empty.counter.update(expand_counter)
         return empty
+    ccs = dc_whole.ccs
+    planes = None
+    if modes.featurize_mode == "device":
+        # None for a ZMW off the fast path: it keeps the host rows.
+        planes = featurize_device.build_planes(dc_whole)
+    if planes is not None:
+        # Same windows, counters and triage as below; a model-bound
+        # window is two table entries instead of an [R, L] matrix.
+        # Device passthrough: a skipped window is a table entry as well,
+        # when the ZMW's CCS qualities fit the uint8 code.
+        if modes.passthrough_mode == "device":
+            planes.ccs_q = featurize_device.encode_ccs_qualities(
+                ccs.base_quality_scores
+            )
+            if (planes.ccs_q is not None
+                    and planes.ccs_q.shape != planes.ccs.shape):
+                planes.ccs_q = None
+        return _plane_zmw_windows(
+            zmw, planes, dc_whole.iter_window_specs(), planes.ccs,
+            planes.ccs_q is not None, dc_whole.name, ccs, options,
+            dc_whole.counter, expand_counter,
+        )
     # Worker-side finishing, keeping the serial batch loop thin: the
     # fast path applies format_rows' PW/IP/SN clipping at ZMW level and
     # emits int16 matrices directly (integral-after-truncation for the
@@ -335,46 +326,18 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
     model_rows: List[np.ndarray] = []
     window_pos: List[int] = []
     skipped: List[stitch_utils.DCModelOutput] = []
-    ccs = dc_whole.ccs
-    planes = None
-    if resolve_featurize_mode(options) == "device":
-        # None for a ZMW off the fast path: it keeps the host rows.
-        planes = featurize_device.build_planes(dc_whole)
-    if planes is not None:
-        # Same windows, counters and triage as below; a model-bound
-        # window is two table entries instead of an [R, L] matrix.
-        # Device passthrough: a skipped window is a table entry as well,
-        # when the ZMW's CCS qualities fit the uint8 code.
-        if resolve_passthrough_mode(options) == "device":
-            planes.ccs_q = featurize_device.encode_ccs_qualities(
-                ccs.base_quality_scores
-            )
-            if (planes.ccs_q is not None
-                    and planes.ccs_q.shape != planes.ccs.shape):
-                planes.ccs_q = None
-        has_model, has_table, window_pos, skipped = _triage_windows(
-            planes, dc_whole.iter_window_specs(), planes.ccs,
-            planes.ccs_q is not None, dc_whole.name, ccs, options,
-        )
-        if not has_table:
-            planes.ccs_q = None  # nothing reads it
-        if not has_model:
-            # Without model windows only the passthrough table needs the
-            # planes, and of them only ccs and ccs_q.
-            planes = planes.without_subreads() if has_table else None
-    else:
-        for f in dc_whole.iter_feature_dicts(
-            pw_max=featurize_device.PW_MAX, ip_max=featurize_device.IP_MAX,
-            sn_max=featurize_device.SN_MAX,  # config.py:89-92 defaults
-            out_dtype=np.int16,
+    for f in dc_whole.iter_feature_dicts(
+        pw_max=featurize_device.PW_MAX, ip_max=featurize_device.IP_MAX,
+        sn_max=featurize_device.SN_MAX,  # config.py:89-92 defaults
+        out_dtype=np.int16,
+    ):
+        if _skip_window(
+            f["overflow"], f["ccs_base_quality_scores"], options
         ):
-            if _skip_window(
-                f["overflow"], f["ccs_base_quality_scores"], options
-            ):
-                skipped.append(process_skipped_window(f, options))
-                continue
-            model_rows.append(f["subreads"][:, :, 0])
-            window_pos.append(int(f["window_pos"]))
+            skipped.append(process_skipped_window(f, options))
+            continue
+        model_rows.append(f["subreads"][:, :, 0])
+        window_pos.append(int(f["window_pos"]))
     counter = dc_whole.counter
     if expand_counter:
         counter.update(expand_counter)
@@ -385,20 +348,20 @@ def preprocess_one_zmw(one_zmw) -> ZmwWindows:
         skipped=skipped,
         counter=counter,
         ec=ccs.ec, np_num_passes=ccs.np_num_passes, rq=ccs.rq, rg=ccs.rg,
-        planes=planes,
     )
 
 
-def _triage_windows(planes, specs, ccs_ids, table_ok, name, ccs,
-                    options: InferenceOptions):
-    """Skip triage over the window specs of one ZMW on the plane path,
-    shared by spaced planes and unspaced ZMWs: fills the window table and
-    the passthrough table of ``planes`` and returns (has model windows,
-    has table entries, window_pos of the model windows, skipped objects).
+def _plane_zmw_windows(zmw, planes, specs, ccs_ids, table_ok, name, ccs,
+                       options: InferenceOptions, counter,
+                       expand_counter) -> ZmwWindows:
+    """ZmwWindows of a ZMW on the plane path, shared by spaced planes and
+    unspaced ZMWs: skip triage over the window ``specs`` into the window
+    table and the passthrough table of ``planes``.
 
     ``ccs_ids`` are the spaced CCS base ids. A skipped window becomes a
     passthrough table entry when ``table_ok`` (device passthrough and CCS
-    qualities that fit the uint8 code), an object otherwise.
+    qualities that fit the uint8 code), an object under ``name`` otherwise.
+    ``counter`` holds the window counters; ``expand_counter`` joins it.
     """
     win_start: List[int] = []
     win_w: List[int] = []
@@ -430,11 +393,26 @@ def _triage_windows(planes, specs, ccs_ids, table_ok, name, ccs,
             c.astype(np.int32) for c in cols[:3]
         )
         planes.pt_pos = cols[3]
-    return bool(win_start), bool(pt), window_pos, skipped
+    planes.need_q(bool(pt))  # only a passthrough table reads the ccs_q plane
+    if not win_start:
+        # Without model windows only the passthrough table needs the
+        # planes, and of them only the CCS row.
+        planes = planes.without_subreads() if pt else None
+    if expand_counter:
+        counter.update(expand_counter)
+    return ZmwWindows(
+        name=zmw,
+        window_pos=np.asarray(window_pos, np.int64),
+        rows=None,
+        skipped=skipped,
+        counter=counter,
+        ec=ccs.ec, np_num_passes=ccs.np_num_passes, rq=ccs.rq, rg=ccs.rg,
+        planes=planes,
+    )
 
 
 def _unspaced_zmw_windows(zmw, unspaced, ccs, options: InferenceOptions,
-                          expand_counter) -> ZmwWindows:
+                          modes: Modes, expand_counter) -> ZmwWindows:
     """ZmwWindows of a ZMW that ships unspaced (spacing_mode "device"):
     windows, counters and triage from the CCS row, which follows from
     ``ins_max`` before any read is spaced."""
@@ -447,24 +425,9 @@ def _unspaced_zmw_windows(zmw, unspaced, ccs, options: InferenceOptions,
         windows_lib.fixed_window_widths(ccs_width, unspaced.max_length),
         counter,
     )
-    has_model, has_table, window_pos, skipped = _triage_windows(
-        unspaced, specs, ccs_ids,
-        resolve_passthrough_mode(options) == "device", zmw, ccs, options,
-    )
-    unspaced.want_q = has_table
-    planes = unspaced
-    if not has_model:
-        planes = unspaced.without_subreads() if has_table else None
-    if expand_counter:
-        counter.update(expand_counter)
-    return ZmwWindows(
-        name=zmw,
-        window_pos=np.asarray(window_pos, np.int64),
-        rows=None,
-        skipped=skipped,
-        counter=counter,
-        ec=ccs.ec, np_num_passes=ccs.np_num_passes, rq=ccs.rq, rg=ccs.rg,
-        planes=planes,
+    return _plane_zmw_windows(
+        zmw, unspaced, specs, ccs_ids, modes.passthrough_mode == "device",
+        zmw, ccs, options, counter, expand_counter,
     )
 
 
@@ -611,231 +574,8 @@ def _gap_tripwire(runner, rows_t, bases_np, gap_frac, n_chunk):
 _SEQ_LUT = np.frombuffer(constants.SEQ_VOCAB.encode("ascii"), np.uint8)
 
 
-class _ModelChunks:
-    """The model input of one ZMW batch, produced batch_size windows at a
-    time; the chunk loop of run_model_on_zmws and
-    run_model_and_stitch_on_zmws.
-
-    Host rows (featurize_mode "host"): the pre-stacked per-ZMW matrices
-    are concatenated once and each chunk is staged through a pinned
-    buffer. Planes (featurize_mode "device"): the batch's planes and
-    tables cross to the device in one copy and each chunk is expanded
-    there by the window_featurize kernel; ZMWs that kept host rows have
-    theirs copied into their slots. On a non-native runner the kernel's
-    numpy twin expands the chunk on the host.
-    """
-
-    def __init__(self, zmws: List[ZmwWindows], runner: InferenceRunner,
-                 options: InferenceOptions):
-        self.runner = runner
-        self.batch_size = options.batch_size
-        self.model_zmws = [
-            z for z in zmws if featurize_device.n_model_windows(z)
-        ]
-        self.all_pos = (
-            np.concatenate([z.window_pos for z in self.model_zmws])
-            if self.model_zmws else np.empty(0, np.int64)
-        )
-        # Native path: features are non-negative and <= SN_MAX (500)
-        # after clipping, and the embed kernel casts to int anyway, so
-        # int16 staging halves H2D traffic with bit-identical results
-        # (numpy's truncation toward zero == the kernel's (int)v == the
-        # torch model's .long()).
-        self.native = bool(getattr(runner, "native", False))
-        self.use_graph = (
-            self.native and os.environ.get("DC_SERVE_GRAPH", "1") != "0"
-        )
-        self.batch: Optional[featurize_device.FeaturizeBatch] = None
-        # ZMWs with something to pack: model windows, or (passthrough_mode
-        # "device") passthrough table entries. A batch of the latter alone
-        # still crosses to the device: its CCS planes are the source of the
-        # passthrough fill.
-        self.packed_zmws = [
-            z for z in zmws
-            if featurize_device.n_model_windows(z)
-            or featurize_device.n_table_passthrough(z)
-        ]
-        if any(getattr(z, "planes", None) is not None
-               for z in self.packed_zmws):
-            self._init_planes()
-        elif self.model_zmws:
-            all_rows = np.concatenate([z.rows for z in self.model_zmws])
-            self.row_length = all_rows.shape[2]
-            if not self.native:
-                all_rows = all_rows.astype(np.float32)
-            self.all_rows = all_rows
-            self.n_model = len(all_rows)
-            self.pinned: Dict[Tuple[int, ...], torch.Tensor] = {}
-        else:
-            self.row_length = options.max_length
-            self.n_model = 0
-
-    def _init_planes(self) -> None:
-        if not self.native:
-            self.batch = featurize_device.pack_batch(self.packed_zmws)
-            expand_device.expand_batch_numpy(self.batch)
-            spacing_device.space_batch_numpy(self.batch)
-        else:
-            device = self.runner.device
-            staging: List[torch.Tensor] = []
-
-            def alloc(nbytes: int) -> np.ndarray:
-                staging.append(
-                    torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-                )
-                return staging[-1].numpy()
-
-            # With the graph every chunk is batch_size table entries:
-            # the tail is padded with -1 (zero) windows once, here.
-            self.batch = batch = featurize_device.pack_batch(
-                self.packed_zmws,
-                pad_multiple=self.batch_size if self.use_graph else 1,
-                alloc=alloc, device_planes=True,
-            )
-            blob = staging[0].to(device, non_blocking=True)
-            planes = None
-            if batch.device_planes:
-                # Unspaced ZMWs: the plane region is born on the device,
-                # zero-filled, in pack_batch's layout.
-                planes = torch.zeros(batch.plane_nbytes, dtype=torch.uint8,
-                                     device=device)
-
-            def view(name: str, array: np.ndarray) -> torch.Tensor:
-                if planes is not None and name in batch.plane_layout:
-                    lo, dtype, count = batch.plane_layout[name]
-                    flat = planes[lo : lo + count * np.dtype(dtype).itemsize]
-                    return flat.view(getattr(torch, np.dtype(dtype).name))
-                lo = batch.offsets[name]
-                flat = blob[lo : lo + array.nbytes]
-                return flat.view(getattr(torch, array.dtype.name))
-
-            self.dev = (
-                view("sub", batch.sub), view("ccs", batch.ccs),
-                view("ccs_bq", batch.ccs_bq),
-                view("zmw_tab", batch.zmw_tab).view(batch.zmw_tab.shape),
-            )
-            self.win_tab = view("win_tab", batch.win_tab).view(
-                batch.win_tab.shape
-            )
-            # Inputs of passthrough_fill_into, ahead of the LUT.
-            self.pt_dev = (
-                self.dev[1], view("ccs_q", batch.ccs_q), self.dev[3],
-                view("pt_tab", batch.pt_tab).view(batch.pt_tab.shape),
-            )
-            if batch.spacing is not None:
-                self._space_on_device(view, staging[1:])
-            if batch.fallback_rows is not None:
-                self.fallback_rows = torch.from_numpy(
-                    batch.fallback_rows
-                ).to(device)
-                self.fallback_idx = torch.from_numpy(
-                    batch.fallback_idx
-                ).to(device)
-        self.n_model = self.batch.n_windows
-        self.row_length = self.batch.max_length
-
-    def _space_on_device(self, view, staged: List[torch.Tensor]) -> None:
-        """Fills the device planes of the unspaced ZMWs: one copy of the
-        packed reads, then the subread_space kernel, on the stream of the
-        kernels that read the planes. ZMWs spaced on the host have their
-        planes copied into their slices. With raw ZMWs (expand_mode
-        "device") ``src`` is allocated on the device, the host-written part
-        copied in, and the cigar_expand kernel fills the rest from the
-        expand blob ahead of subread_space."""
-        batch, sp = self.batch, self.batch.spacing
-        device = self.runner.device
-        sp_blob = staged[0].to(device, non_blocking=True)
-
-        def sp_view(name: str, array: np.ndarray, dtype) -> torch.Tensor:
-            lo = sp.offsets[name]
-            return sp_blob[lo : lo + array.nbytes].view(dtype)
-
-        src = sp_view("src", sp.src, torch.uint8)
-        if sp.expand is not None:
-            ex = sp.expand
-            ex_blob = staged[1].to(device, non_blocking=True)
-
-            def ex_view(name: str, array: np.ndarray, dtype) -> torch.Tensor:
-                lo = ex.offsets[name]
-                return ex_blob[lo : lo + array.nbytes].view(dtype)
-
-            host_src = src
-            src = torch.empty(sp.n_src, dtype=torch.uint8, device=device)
-            src[: sp.n_src_host].copy_(host_src)
-            self.runner.ext.cigar_expand_into(
-                ex_view("raw", ex.raw, torch.uint8),
-                ex_view("op_tab", ex.op_tab, torch.int32).view(
-                    ex.op_tab.shape),
-                ex_view("xr_tab", ex.xr_tab, torch.int64).view(
-                    ex.xr_tab.shape),
-                src, torch.from_numpy(expand_device.NT16_LUT),
-            )
-
-        sub, ccs, ccs_bq, zmw_tab = self.dev
-        ccs_q = self.pt_dev[1]
-        targets = dict(sub=sub, ccs=ccs, ccs_bq=ccs_bq, ccs_q=ccs_q)
-        for name, off, array in batch.host_planes:
-            targets[name][off : off + array.size].copy_(
-                torch.from_numpy(array))
-        ins_max = sp_view("ins_max", sp.ins_max, torch.int16)
-        self.runner.ext.subread_space_into(
-            src, ins_max,
-            sp_view("sp_tab", sp.sp_tab, torch.int64).view(sp.sp_tab.shape),
-            sp_view("read_tab", sp.read_tab, torch.int64).view(
-                sp.read_tab.shape),
-            zmw_tab, torch.empty(ins_max.numel(), dtype=torch.int32,
-                                 device=self.runner.device),
-            sub, ccs, ccs_q, ccs_bq, batch.use_ccs_bq,
-        )
-
-    def chunk(self, i: int) -> Tuple[torch.Tensor, int]:
-        """(rows_t, n_valid) for windows [i, i + batch_size): the model
-        input (padded to batch_size when the graph is in use) and the
-        number of real windows in it."""
-        if self.batch is not None:
-            return self._chunk_from_planes(i)
-        chunk = np.ascontiguousarray(self.all_rows[i : i + self.batch_size])
-        n_valid = len(chunk)
-        rows_t = torch.from_numpy(chunk)
-        if self.native:
-            # Fixed-shape pinned buffer: partial tails are zero-padded
-            # so the hipGraph-captured step replays at one shape (pad
-            # windows cost compute on the final chunk only; their
-            # outputs are sliced away).
-            shape = (
-                (self.batch_size,) + rows_t.shape[1:]
-                if self.use_graph
-                else tuple(rows_t.shape)
-            )
-            buf = self.pinned.get(shape)
-            if buf is None:
-                buf = torch.zeros(shape, dtype=rows_t.dtype).pin_memory()
-                self.pinned[shape] = buf
-            buf[:n_valid].copy_(rows_t)
-            if self.use_graph and n_valid < shape[0]:
-                buf[n_valid:].zero_()
-            rows_t = buf
-        return rows_t, n_valid
-
-    def _chunk_from_planes(self, i: int) -> Tuple[torch.Tensor, int]:
-        batch = self.batch
-        n_valid = min(self.batch_size, self.n_model - i)
-        if not self.native:
-            rows = featurize_device.featurize_chunk_numpy(
-                batch, i, i + n_valid
-            )
-            return torch.from_numpy(rows.astype(np.float32)), n_valid
-        hi = i + (self.batch_size if self.use_graph else n_valid)
-        rows_t = self.runner.ext.window_featurize(
-            *self.dev, self.win_tab[i:hi], batch.n_rows, batch.max_length,
-            batch.max_passes, batch.use_ccs_bq,
-        )
-        k0, k1 = batch.fallback_range(i, i + n_valid)
-        if k1 > k0:
-            rows_t.index_copy_(
-                0, self.fallback_idx[k0:k1] - i, self.fallback_rows[k0:k1]
-            )
-        return rows_t, n_valid
+# The model input of a ZMW batch and its chunk loop live in model_chunks.py.
+_ModelChunks = model_chunks_lib.model_chunks
 
 
 def run_model_on_zmws(
@@ -866,15 +606,7 @@ def run_model_on_zmws(
     for z in chunks.model_zmws:
         owners.extend([z] * featurize_device.n_model_windows(z))
     all_pos = chunks.all_pos
-    use_graph = chunks.use_graph
-    for i in range(0, chunks.n_model, options.batch_size):
-        rows_t, n_valid = chunks.chunk(i)
-        if use_graph:
-            bases_t, quals_t = runner.forward_windows_graphed(rows_t)
-            bases_t = bases_t[:n_valid]
-            quals_t = quals_t[:n_valid]
-        else:
-            bases_t, quals_t = runner.forward_windows(rows_t)
+    for i, rows_t, bases_t, quals_t, n_valid in chunks.forward():
         bases_np = bases_t.cpu().numpy()
         _gap_tripwire(
             runner, rows_t, bases_np, float((bases_np == 0).mean()),
@@ -945,7 +677,7 @@ def run_model_and_stitch_on_zmws(
     n_model_bytes = n_model * row_length
     n_table_bytes = plan.n_table_bytes
     n_total = plan.n_source_bytes
-    if n_table_bytes != (chunks.batch.n_pt_bytes if chunks.batch else 0):
+    if n_table_bytes != chunks.n_pt_bytes:
         raise ValueError(
             "stitch plan and packed passthrough table disagree on the "
             "size of the passthrough region"
@@ -961,17 +693,9 @@ def run_model_and_stitch_on_zmws(
                           device=runner.device)
     else:
         acc_np = np.empty((2, n_total), np.uint8)
-    use_graph = chunks.use_graph
-    for i in range(0, n_model, options.batch_size):
-        # The per-chunk gap count below synchronises, so the staging
-        # buffer is free again before the next chunk overwrites it.
-        rows_t, n_valid = chunks.chunk(i)
-        if use_graph:
-            bases_t, quals_t = runner.forward_windows_graphed(rows_t)
-            bases_t = bases_t[:n_valid]
-            quals_t = quals_t[:n_valid]
-        else:
-            bases_t, quals_t = runner.forward_windows(rows_t)
+    # The per-chunk gap count below synchronises, so the staging buffer is
+    # free again before the next chunk overwrites it.
+    for i, rows_t, bases_t, quals_t, n_valid in chunks.forward():
         lo, hi = i * row_length, (i + n_valid) * row_length
         if native:
             # The graph's output buffer is rewritten by the next replay:
@@ -997,10 +721,8 @@ def run_model_and_stitch_on_zmws(
         out_off = np.zeros(1, np.int32)
     elif native:
         if n_table_bytes:
-            # One launch per ZMW batch, on the stream of the model loop and
-            # of stitch_compact, which reads what it writes.
-            runner.ext.passthrough_fill_into(
-                *chunks.pt_dev, _runner_quality_lut(runner, options, True),
+            chunks.fill_passthrough(
+                _runner_quality_lut(runner, options, True),
                 acc[0, n_model_bytes:extra_lo],
                 acc[1, n_model_bytes:extra_lo],
             )
@@ -1026,9 +748,7 @@ def run_model_and_stitch_on_zmws(
         qual_out = packed[n_off + n_kept :]
     else:
         if n_table_bytes:
-            batch = chunks.batch
-            featurize_device.passthrough_fill_numpy(
-                batch.ccs, batch.ccs_q, batch.zmw_tab, batch.pt_tab,
+            chunks.fill_passthrough(
                 _runner_quality_lut(runner, options, False),
                 acc_np[0, n_model_bytes:extra_lo],
                 acc_np[1, n_model_bytes:extra_lo],
@@ -1208,11 +928,9 @@ def run(
     """Performs an inference run (quick_inference.py:794-963)."""
     t_start = time.time()
     options = options or InferenceOptions()
-    resolve_featurize_mode(options)  # a bad value fails here, not in a worker
-    resolve_passthrough_mode(options)  # so does a mode combination
-    resolve_spacing_mode(options)
-    resolve_expand_mode(options)
-    if resolve_stitch_mode(options) == "device":
+    # A bad value or mode combination fails here, not in a worker.
+    stitch_mode = resolve_modes(options).stitch_mode
+    if stitch_mode == "device":
         stitch_device.check_max_base_quality(options.max_base_quality)
 
     # Load params + model. checkpoint == 'random' builds a random-init model
@@ -1328,7 +1046,6 @@ def run(
         before = time.time()
         n_model = sum(z.n_model for z in outputs)
         n_skipped = sum(z.n_skipped for z in outputs)
-        stitch_mode = resolve_stitch_mode(options)
         if stitch_mode == "device":
             preds = run_model_and_stitch_on_zmws(outputs, runner, options)
         else:

@@ -28,10 +28,12 @@ writes their base ids and QVs into the stitch buffer.
 from __future__ import annotations
 
 import dataclasses
+import functools
 from typing import Any, Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from deepconsensus_amd.preprocess import blob as blob_lib
 from deepconsensus_amd.preprocess.windows import DcExample
 from deepconsensus_amd.utils import constants
 
@@ -49,34 +51,65 @@ def tensor_height(max_passes: int, use_ccs_bq: bool) -> int:
     return 4 * max_passes + 1 + int(bool(use_ccs_bq)) + 4
 
 
-@dataclasses.dataclass
-class ZmwPlanes:
+@dataclasses.dataclass(kw_only=True)
+class ZmwTables:
+    """What ZmwWindows.planes holds for one ZMW on the plane path, whichever
+    stage its reads are in: the window table, the passthrough table and the
+    per-read constants. ZmwPlanes (spaced planes), spacing_device.ZmwUnspaced
+    (reads before spacing) and expand_device.ZmwRaw (records before
+    expansion) add the reads; each says how many it keeps (``n_sub``), how
+    wide its planes are (``width``), whether it carries the ccs_bq and ccs_q
+    planes (``has_bq``, ``wants_q``; ``need_q`` drops the latter) and what
+    remains of it without model windows (``without_subreads``)."""
+
+    unspaced = False  # the planes are built on the device (spacing_device)
+    raw_records = False  # ... from reads born on the device (expand_device)
+
+    strand: np.ndarray  # uint8 [n_sub]
+    sn: np.ndarray  # int16 [4], clipped to 0..SN_MAX
+    max_passes: int
+    max_length: int
+    win_start: np.ndarray = blob_lib.empty_column(np.int32)  # model-bound
+    win_w: np.ndarray = blob_lib.empty_column(np.int32)  # windows only
+    # Passthrough table (passthrough_mode "device"): one entry per skipped
+    # window, columns [start, start + w) padded to ``width`` (above
+    # max_length for an overflow window). Empty when the ZMW keeps host
+    # ``skipped`` objects.
+    pt_start: np.ndarray = blob_lib.empty_column(np.int32)
+    pt_w: np.ndarray = blob_lib.empty_column(np.int32)
+    pt_width: np.ndarray = blob_lib.empty_column(np.int32)
+    pt_pos: np.ndarray = blob_lib.empty_column(np.int64)  # window_pos
+
+    @property
+    def n_windows(self) -> int:
+        return len(self.win_start)
+
+    @property
+    def n_passthrough(self) -> int:
+        return len(self.pt_start)
+
+    def _no_subreads(self) -> dict:
+        """The read fields of the subclass, emptied."""
+        raise NotImplementedError
+
+    def without_subreads(self):
+        """What a ZMW without model windows still needs: the CCS row."""
+        return dataclasses.replace(
+            self, strand=np.empty(0, np.uint8), sn=np.zeros(4, np.int16),
+            **self._no_subreads())
+
+
+@dataclasses.dataclass(kw_only=True)
+class ZmwPlanes(ZmwTables):
     """Compact model input of one ZMW: ``n_sub = min(n_subreads,
     max_passes)`` subreads over the spaced width W."""
 
     sub: np.ndarray  # uint8 [3, n_sub, W]: base ids, pw, ip
-    strand: np.ndarray  # uint8 [n_sub]
-    sn: np.ndarray  # int16 [4], clipped to 0..SN_MAX
     ccs: np.ndarray  # uint8 [W] CCS base ids
     ccs_bq: Optional[np.ndarray]  # int16 [W], only with use_ccs_bq
-    win_start: np.ndarray  # int32 [n_model], model-bound windows only
-    win_w: np.ndarray  # int32 [n_model]
-    max_passes: int
-    max_length: int
-    # Passthrough table (passthrough_mode "device"): one entry per skipped
-    # window, columns [start, start + w) padded to ``width`` (above
-    # max_length for an overflow window). ``ccs_q`` is the CCS quality of
-    # every column coded q + 1 (0 = the -1 padding value); None means the
-    # ZMW keeps host ``skipped`` objects and the table is empty.
+    # CCS quality of every column coded q + 1 (0 = the -1 padding value);
+    # None means the passthrough table is empty.
     ccs_q: Optional[np.ndarray] = None  # uint8 [W]
-    pt_start: np.ndarray = dataclasses.field(
-        default_factory=lambda: np.empty(0, np.int32))
-    pt_w: np.ndarray = dataclasses.field(
-        default_factory=lambda: np.empty(0, np.int32))
-    pt_width: np.ndarray = dataclasses.field(
-        default_factory=lambda: np.empty(0, np.int32))
-    pt_pos: np.ndarray = dataclasses.field(  # window_pos per entry
-        default_factory=lambda: np.empty(0, np.int64))
 
     @property
     def n_sub(self) -> int:
@@ -86,13 +119,20 @@ class ZmwPlanes:
     def width(self) -> int:
         return self.ccs.shape[0]
 
-    def without_subreads(self) -> "ZmwPlanes":
-        """The planes a ZMW without model windows still needs: ccs and
-        ccs_q; ``sub`` shrinks to [3, 0, W]."""
-        return dataclasses.replace(
-            self, sub=np.empty((3, 0, self.width), np.uint8),
-            strand=np.empty(0, np.uint8), sn=np.zeros(4, np.int16),
-        )
+    @property
+    def has_bq(self) -> bool:
+        return self.ccs_bq is not None
+
+    @property
+    def wants_q(self) -> bool:
+        return self.ccs_q is not None
+
+    def need_q(self, needed: bool) -> None:
+        if not needed:
+            self.ccs_q = None
+
+    def _no_subreads(self) -> dict:
+        return dict(sub=np.empty((3, 0, self.width), np.uint8))
 
 
 def encode_ccs_qualities(qualities: Any) -> Optional[np.ndarray]:
@@ -109,12 +149,17 @@ def encode_ccs_qualities(qualities: Any) -> Optional[np.ndarray]:
     return (q.astype(np.int64) + 1).astype(np.uint8)
 
 
-def _encode_bases(bases: np.ndarray) -> np.ndarray:
-    enc = np.zeros(bases.shape, np.uint8)
-    for k, base in enumerate(constants.SEQ_VOCAB):
-        if k:
-            enc[bases == base] = k
-    return enc
+# Code point -> base id; anything outside the vocabulary is id 0.
+_BASE_LUT = np.zeros(128, np.uint8)
+for _k, _base in enumerate(constants.SEQ_VOCAB):
+    if _k:
+        _BASE_LUT[ord(_base)] = _k
+
+
+def encode_bases(bases: np.ndarray) -> np.ndarray:
+    """Base ids of a ``<U1`` array in one table lookup."""
+    cp = np.ascontiguousarray(bases).view(np.uint32)
+    return _BASE_LUT[np.minimum(cp, 127)]
 
 
 def build_planes(dc: DcExample) -> Optional[ZmwPlanes]:
@@ -136,7 +181,7 @@ def build_planes(dc: DcExample) -> Optional[ZmwPlanes]:
     sub = np.zeros((3, n, W), np.uint8)
     sn = np.zeros(4, np.int16)
     if n:
-        sub[0] = _encode_bases(np.stack([r.bases for r in subs]))
+        sub[0] = encode_bases(np.stack([r.bases for r in subs]))
         # uint8 is 0..255 already; the clip documents format_rows' bound.
         np.clip(np.stack([r.pw for r in subs]), 0, PW_MAX, out=sub[1])
         np.clip(np.stack([r.ip for r in subs]), 0, IP_MAX, out=sub[2])
@@ -154,10 +199,8 @@ def build_planes(dc: DcExample) -> Optional[ZmwPlanes]:
         sub=sub,
         strand=np.array([int(r.strand) for r in subs], np.uint8),
         sn=sn,
-        ccs=_encode_bases(dc.ccs.bases),
+        ccs=encode_bases(dc.ccs.bases),
         ccs_bq=ccs_bq,
-        win_start=np.empty(0, np.int32),
-        win_w=np.empty(0, np.int32),
         max_passes=config.max_passes,
         max_length=config.max_length,
     )
@@ -168,16 +211,15 @@ def n_model_windows(z: Any) -> int:
     (``rows`` or ``planes``) it carries them in."""
     if z.rows is not None:
         return len(z.rows)
-    if getattr(z, "planes", None) is not None:
-        return len(z.planes.win_start)
-    return 0
+    planes = getattr(z, "planes", None)
+    return 0 if planes is None else planes.n_windows
 
 
 def n_table_passthrough(z: Any) -> int:
     """Skipped windows a ZmwWindows-like object carries as passthrough
     table entries of its planes (not as ``skipped`` objects)."""
     planes = getattr(z, "planes", None)
-    return 0 if planes is None else len(planes.pt_start)
+    return 0 if planes is None else planes.n_passthrough
 
 
 # Columns of a pt_tab row.
@@ -257,8 +299,7 @@ class FeaturizeBatch:
     use_ccs_bq: bool
     fallback_idx: np.ndarray  # int64, ascending window indices
     fallback_rows: Optional[np.ndarray]  # int16 [len(fallback_idx), R, L]
-    ccs_q: np.ndarray = dataclasses.field(
-        default_factory=lambda: np.empty(0, np.uint8))
+    ccs_q: np.ndarray = blob_lib.empty_column(np.uint8)
     pt_tab: np.ndarray = dataclasses.field(
         default_factory=lambda: np.empty((0, 5), np.int32))
     n_pt_bytes: int = 0
@@ -287,23 +328,7 @@ class FeaturizeBatch:
         return int(k0), int(k1)
 
 
-def _check(cond: bool, message: str) -> None:
-    if not cond:
-        raise ValueError(f"pack_batch: {message}")
-
-
-def _has_bq(p: Any) -> bool:
-    """Whether a ZmwPlanes or ZmwUnspaced carries the ccs_bq plane."""
-    if getattr(p, "unspaced", False):
-        return bool(p.use_ccs_bq)
-    return p.ccs_bq is not None
-
-
-def _wants_q(p: Any) -> bool:
-    """Whether the ccs_q plane of a ZmwPlanes or ZmwUnspaced is filled."""
-    if getattr(p, "unspaced", False):
-        return bool(p.want_q)
-    return p.ccs_q is not None
+_check = functools.partial(blob_lib.check, "pack_batch")
 
 
 def pack_batch(
@@ -333,7 +358,7 @@ def pack_batch(
     outside a plane or when the ZMWs disagree on the layout.
     """
     _check(pad_multiple >= 1, "pad_multiple must be positive")
-    plane_zmws: List[ZmwPlanes] = []
+    plane_zmws: List[ZmwTables] = []
     win_parts: List[np.ndarray] = []
     fb_idx: List[np.ndarray] = []
     fb_rows: List[np.ndarray] = []
@@ -359,9 +384,8 @@ def pack_batch(
             win_parts[-1][:, 1:] = 0
         else:
             p = z.planes
-            unspaced = getattr(p, "unspaced", False)
-            this = (int(p.max_passes), int(p.max_length),
-                    _has_bq(p))
+            unspaced = p.unspaced
+            this = (int(p.max_passes), int(p.max_length), p.has_bq)
             _check(layout in (None, this),
                    f"ZMWs disagree on (max_passes, max_length, "
                    f"use_ccs_bq): {layout} and {this}")
@@ -398,7 +422,7 @@ def pack_batch(
                 _check(p.ccs_q.dtype == np.uint8 and p.ccs_q.shape == (W,),
                        "ccs_q must be uint8 [W]")
             if n_pt:
-                _check(_wants_q(p),
+                _check(p.wants_q,
                        "passthrough table on a ZMW without ccs_q")
                 _check(np.shape(p.pt_w) == np.shape(p.pt_width) == (n_pt,),
                        "pt_start, pt_w and pt_width must be [n_passthrough]")
@@ -420,9 +444,9 @@ def pack_batch(
         pt_all = np.empty((0, 5), np.int64)
     n_pt_bytes = validate_passthrough_table(
         pt_all, [p.width for p in plane_zmws])
-    with_q = any(_wants_q(p) for p in plane_zmws)
+    with_q = any(p.wants_q for p in plane_zmws)
     unspaced_zmws = [(i, p) for i, p in enumerate(plane_zmws)
-                     if getattr(p, "unspaced", False)]
+                     if p.unspaced]
     device_planes = bool(device_planes and unspaced_zmws)
 
     if layout is None:
@@ -451,31 +475,16 @@ def pack_batch(
         ("ccs_q", np.uint8,
          sum(p.width for p in plane_zmws) if with_q else 0),
     ]
-    plane_layout, plane_total = {}, 0
-    for name, dtype, count in plane_sizes:
-        plane_layout[name] = (plane_total, dtype, count)
-        plane_total += count * np.dtype(dtype).itemsize
+    plane_offsets, _ = blob_lib.region_offsets(plane_sizes)
+    plane_layout = {name: (plane_offsets[name], dtype, count)
+                    for name, dtype, count in plane_sizes}
     sizes = [
         ("zmw_tab", np.int64, n_zmw * n_col),
         ("win_tab", np.int32, n_padded * 3),
         ("pt_tab", np.int32, len(pt_all) * 5),
     ] + [(name, dtype, 0 if device_planes else count)
          for name, dtype, count in plane_sizes]
-    # Descending item size, so every view is aligned to its own type.
-    offsets, total = {}, 0
-    for name, dtype, count in sizes:
-        offsets[name] = total
-        total += count * np.dtype(dtype).itemsize
-    blob = np.empty(total, np.uint8) if alloc is None else alloc(total)
-    _check(isinstance(blob, np.ndarray) and blob.dtype == np.uint8
-           and blob.shape == (total,) and blob.flags.c_contiguous,
-           "alloc must return a contiguous uint8 array of nbytes")
-    views = {}
-    for name, dtype, count in sizes:
-        lo = offsets[name]
-        views[name] = blob[lo : lo + count * np.dtype(dtype).itemsize].view(
-            dtype
-        )
+    blob, offsets, views = blob_lib.pack_views(sizes, alloc, "pack_batch")
     zmw_tab = views["zmw_tab"].reshape(n_zmw, n_col)
     win_tab = views["win_tab"].reshape(n_padded, 3)
     zmw_tab[:] = 0
@@ -491,7 +500,7 @@ def pack_batch(
         zmw_tab[i, TAB_W] = W
         zmw_tab[i, TAB_FIXED : TAB_FIXED + n_sub] = p.strand
         zmw_tab[i, TAB_FIXED + max_passes :] = p.sn
-        if getattr(p, "unspaced", False):
+        if p.unspaced:
             # Zero until the spacing kernel (or its twin) fills them.
             pieces = [("sub", sub_off, sub_size, 0), ("ccs", ccs_off, W, 0)]
             if use_ccs_bq:
