@@ -318,6 +318,12 @@ class InferenceRunner:
             # outputs, profiles/r07_persistent_ffn.md); DC_FFN_V5=0 falls
             # through to the v3/v2/v1 chain.
             self.ffn_v5 = _os.environ.get("DC_FFN_V5", "1") != "0"
+            # K7 folded into the v5 FFN as a per-tile prologue (bitwise-equal
+            # outputs, profiles/r14_outproj_ffn.md); DC_FUSED_OUTPROJ=0
+            # restores the fused_linear + fused_ffn_v5 pair.
+            self.fused_outproj = (
+                _os.environ.get("DC_FUSED_OUTPROJ", "1") != "0"
+            )
 
             if self.ffn_fused_ok:
                 for i, l in enumerate(model.layers):
@@ -444,6 +450,14 @@ class InferenceRunner:
                         qkv = (flat @ lw["wqkv_t"]).view(b, l, -1)
                 with trace.range("K6_banded_attn"):
                     a = self._attn(qkv)
+                if self.ffn_fused_ok and self.ffn_v5 and self.fused_outproj:
+                    with trace.range("K7_K9_outproj_ffn"):
+                        flat = self.ext.fused_outproj_ffn(
+                            a.view(b * l, h), flat, lw["wout_pad"],
+                            lw["alpha_attn"], lw["w1_v2"], lw["w2_pad"],
+                            lw["b2_f32"], lw["alpha_ffn"],
+                        )
+                    continue
                 if self.ffn_fused_ok:
                     with trace.range("K7_out_proj"):
                         flat = self.ext.fused_linear(

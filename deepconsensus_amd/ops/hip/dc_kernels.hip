@@ -248,6 +248,10 @@ at::Tensor fused_ffn_v3(at::Tensor x, at::Tensor w1, at::Tensor w2,
                         at::Tensor b2, double alpha);
 at::Tensor fused_ffn_v5(at::Tensor x, at::Tensor w1, at::Tensor w2,
                         at::Tensor b2, double alpha, int64_t max_blocks);
+at::Tensor fused_outproj_ffn(at::Tensor a, at::Tensor resid,
+                             at::Tensor wout, double alpha_attn,
+                             at::Tensor w1, at::Tensor w2, at::Tensor b2,
+                             double alpha_ffn, int64_t max_blocks);
 void embed_grad(at::Tensor rows, at::Tensor grad_out, at::Tensor row_shift,
                 at::Tensor row_vocab, at::Tensor row_tbase,
                 at::Tensor row_width, at::Tensor row_col,
@@ -408,6 +412,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "caps the grid, 0 = one block per CU",
         pybind11::arg("x"), pybind11::arg("w1"), pybind11::arg("w2"),
         pybind11::arg("b2"), pybind11::arg("alpha"),
+        pybind11::arg("max_blocks") = 0);
+  m.def("fused_outproj_ffn", &fused_outproj_ffn,
+        "Attention out-projection + ReZero residual (K7) folded into the "
+        "persistent FFN (K9): v5 with a per-tile prologue that builds its "
+        "A-fragments from a @ Wout^T; max_blocks caps the grid, 0 = one "
+        "block per CU",
+        pybind11::arg("a"), pybind11::arg("resid"),
+        pybind11::arg("wout_pad"), pybind11::arg("alpha_attn"),
+        pybind11::arg("w1_v2"), pybind11::arg("w2_pad"),
+        pybind11::arg("b2_f32"), pybind11::arg("alpha_ffn"),
         pybind11::arg("max_blocks") = 0);
   m.def("embed_grad", &embed_grad,
         "Fused embedding-stack backward (training, all tables, one pass)");
