@@ -18,11 +18,11 @@ import torch
 
 from deepconsensus_amd.models import checkpoint as ckpt_lib
 from deepconsensus_amd.models import config as cfg
-from deepconsensus_amd.models import data as data_lib
+from deepconsensus_amd.models import data_device
 from deepconsensus_amd.models import lamb as lamb_lib
 from deepconsensus_amd.models import losses as losses_lib
 from deepconsensus_amd.models.model import get_model
-from deepconsensus_amd.models.train import _prepare_batch
+from deepconsensus_amd.models.train import _prepare_batch  # noqa: F401
 from deepconsensus_amd.parallel import comm
 
 log = logging.getLogger(__name__)
@@ -84,10 +84,13 @@ def train_model(
     eval_every: int = 3000,
     limit_steps: int = 0,
     use_bf16: bool = False,
+    input_mode: Optional[str] = None,
+    input_workers: Optional[int] = None,
 ) -> dict:
     from deepconsensus_amd.utils.tuned_gemm import enable_tuned_gemms
 
     enable_tuned_gemms()
+    input_mode = data_device.resolve_input_mode(input_mode)
     rank, world = comm.init_distributed()
     main = rank == 0
     os.makedirs(out_dir, exist_ok=True)
@@ -122,8 +125,9 @@ def train_model(
     student_alpha = params.get("student_alpha", 1.0)
     distill_alpha = params.get("distill_alpha", 1.0)
 
-    train_ds = data_lib.DatasetIterator(
-        params.train_path, params, params.batch_size, rank=rank,
+    train_ds = data_device.make_input(
+        params.train_path, params, params.batch_size, device,
+        input_mode=input_mode, input_workers=input_workers, rank=rank,
         world_size=world, seed=params.seed, limit=params.get("limit", -1),
     )
 
@@ -131,9 +135,8 @@ def train_model(
     step = 0
     t0 = time.time()
     for epoch in range(params.num_epochs):
-        for batch in train_ds.iterate(epoch):
+        for rows, label in train_ds.iterate(epoch):
             schedule.apply(optimizer, step)
-            rows, label = _prepare_batch(batch, device)
             reducer.zero_()
             # bf16 autocast: teacher + student forwards take the fused
             # MFMA banded-attention path on GPU (model.py); losses stay
@@ -194,6 +197,12 @@ def main(argv: Optional[List[str]] = None) -> None:
     ap.add_argument("--bf16", action="store_true",
                     help="autocast forwards to bf16 (fused MFMA "
                     "attention path on GPU)")
+    ap.add_argument("--input_mode", default=None,
+                    help="host (default) or device: as for train "
+                    "(DC_INPUT_MODE sets the default)")
+    ap.add_argument("--input_workers", type=int, default=None,
+                    help="reader processes of --input_mode device "
+                    "(0 reads in-process)")
     args = ap.parse_args(argv)
     params = cfg.get_config(args.params)
     if args.train_path:
@@ -209,7 +218,9 @@ def main(argv: Optional[List[str]] = None) -> None:
     )
     train_model(args.out_dir, args.teacher_checkpoint, params,
                 device=device, limit_steps=args.limit_steps,
-                use_bf16=getattr(args, "bf16", False))
+                use_bf16=getattr(args, "bf16", False),
+                input_mode=args.input_mode,
+                input_workers=args.input_workers)
 
 
 if __name__ == "__main__":

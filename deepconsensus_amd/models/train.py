@@ -23,7 +23,8 @@ import torch
 
 from deepconsensus_amd.models import checkpoint as ckpt_lib
 from deepconsensus_amd.models import config as cfg
-from deepconsensus_amd.models import data as data_lib
+from deepconsensus_amd.models import data as data_lib  # noqa: F401
+from deepconsensus_amd.models import data_device
 from deepconsensus_amd.models import lamb as lamb_lib
 from deepconsensus_amd.models import losses as losses_lib
 from deepconsensus_amd.models.model import get_model
@@ -51,8 +52,18 @@ def train_model(
     write_checkpoint_metrics: bool = True,
     warm_start: Optional[str] = None,
     use_bf16: bool = False,
+    input_mode: Optional[str] = None,
+    input_workers: Optional[int] = None,
+    batch_hook=None,
 ) -> dict:
-    """Runs the custom training loop; returns summary metrics."""
+    """Runs the custom training loop; returns summary metrics.
+
+    input_mode host (default; DC_INPUT_MODE overrides) reads through
+    DatasetIterator + _prepare_batch; device reads through
+    data_device.DeviceInputIterator. batch_hook, if given, is called with
+    every (rows, label) training batch before its step.
+    """
+    input_mode = data_device.resolve_input_mode(input_mode)
     from deepconsensus_amd.utils.tuned_gemm import enable_tuned_gemms
 
     enable_tuned_gemms()
@@ -97,12 +108,14 @@ def train_model(
         log.info("resumed from %s (epoch %d step %d)", resume_path,
                  initial_epoch, step)
 
-    train_ds = data_lib.DatasetIterator(
-        params.train_path, params, params.batch_size, rank=rank,
+    train_ds = data_device.make_input(
+        params.train_path, params, params.batch_size, device,
+        input_mode=input_mode, input_workers=input_workers, rank=rank,
         world_size=world, seed=params.seed, limit=params.get("limit", -1),
     )
-    eval_ds = data_lib.DatasetIterator(
-        params.eval_path, params, params.batch_size, shuffle=False,
+    eval_ds = data_device.make_input(
+        params.eval_path, params, params.batch_size, device,
+        input_mode=input_mode, input_workers=input_workers, shuffle=False,
         rank=rank, world_size=world, limit=params.get("limit", -1),
     )
 
@@ -113,8 +126,7 @@ def train_model(
         yield_metric = losses_lib.YieldOverCCSMetric()
         total_loss, n_batches = 0.0, 0
         with torch.no_grad():
-            for batch in eval_ds.iterate():
-                rows, label = _prepare_batch(batch, device)
+            for rows, label in eval_ds.iterate():
                 probs = model(rows, training=False)
                 loss = loss_fn(label, probs.float()) / max(
                     label.shape[0], 1
@@ -150,9 +162,10 @@ def train_model(
         eval_writer = EventWriter(os.path.join(out_dir, "summaries",
                                                "eval"))
     for epoch in range(initial_epoch, params.num_epochs):
-        for batch in train_ds.iterate(epoch):
+        for rows, label in train_ds.iterate(epoch):
             lr = schedule.apply(optimizer, step)
-            rows, label = _prepare_batch(batch, device)
+            if batch_hook is not None:
+                batch_hook(rows, label)
             reducer.zero_()
             # bf16 autocast (BASELINE config #4): GEMMs/attention run bf16,
             # LN/softmax and the alignment loss stay fp32; fp32 master
@@ -257,6 +270,16 @@ def main(argv: Optional[List[str]] = None) -> None:
     ap.add_argument("--device", default=None)
     ap.add_argument("--bf16", action="store_true",
                     help="autocast forward to bf16 (fp32 loss/LN/softmax)")
+    ap.add_argument("--input_mode", default=None,
+                    help="host (default): decode, format and upload every "
+                    "example on the main thread; device: reader workers "
+                    "move raw payloads, the shuffle buffer lives on the "
+                    "device and a HIP kernel assembles each batch. Same "
+                    "batches, same order. DC_INPUT_MODE sets the default")
+    ap.add_argument("--input_workers", type=int, default=None,
+                    help="reader processes of --input_mode device "
+                    "(default: half the CPUs, at most 8; 0 reads "
+                    "in-process)")
     ap.add_argument("--write_checkpoint_metrics", type=lambda v: v != "false",
                     default=True,
                     help="append eval metrics to checkpoint_metrics.tsv")
@@ -294,6 +317,8 @@ def main(argv: Optional[List[str]] = None) -> None:
                 limit_steps=args.limit_steps,
                 write_checkpoint_metrics=args.write_checkpoint_metrics,
                 warm_start=args.checkpoint, use_bf16=args.bf16,
+                input_mode=args.input_mode,
+                input_workers=args.input_workers,
             )
             break
         except RuntimeError as e:

@@ -38,6 +38,7 @@ _SRCS = [
     os.path.join(_OPS_DIR, "hip", "alignment_calib.hip"),
     os.path.join(_OPS_DIR, "hip", "cigar_expand.hip"),
     os.path.join(_OPS_DIR, "hip", "fused_outproj_ffn.hip"),
+    os.path.join(_OPS_DIR, "hip", "batch_assemble.hip"),
 ]
 EXT_NAME = "dc_hip_kernels"
 

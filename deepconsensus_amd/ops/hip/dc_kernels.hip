@@ -345,8 +345,25 @@ void cigar_expand_into(at::Tensor raw, at::Tensor op_tab, at::Tensor xr_tab,
                        at::Tensor src, at::Tensor lut);
 int64_t cigar_expand_tile();
 int64_t cigar_expand_stage();
+// Defined in batch_assemble.hip.
+void batch_assemble_into(at::Tensor pool, at::Tensor upload, int64_t n_in,
+                         at::Tensor gather, at::Tensor rows, at::Tensor label,
+                         int64_t max_passes, bool use_ccs_bq, double pw_max,
+                         double ip_max, double sn_max,
+                         bool remove_label_gaps);
+void pool_store(at::Tensor pool, at::Tensor upload, at::Tensor scatter);
+int64_t batch_assemble_slot_floats(int64_t R, int64_t L);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("batch_assemble_into", &batch_assemble_into,
+        "Device training input: gather examples out of the HBM shuffle pool "
+        "or this step's upload, clip PW/IP/SN rows, optionally left-shift "
+        "labels -> caller-owned fp32 rows [B, R, L] and label [B, L]");
+  m.def("pool_store", &pool_store,
+        "Device training input: move upload rows into their pool slots "
+        "(-1 skips; the last writer of a slot wins)");
+  m.def("batch_assemble_slot_floats", &batch_assemble_slot_floats,
+        "Floats per pool / upload slot for an [R, L] example");
   m.def("cigar_expand_into", &cigar_expand_into,
         "Device alignment expansion: record operands + op tables -> the "
         "unspaced reads (codes | pw | ip) in the caller-owned src of "
