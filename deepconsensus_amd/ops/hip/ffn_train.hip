@@ -109,20 +109,21 @@ __global__ __launch_bounds__(512, 1) void ffn_train_kernel(
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
       }
 
-      // Intermediate element (m, hidden) for lane (c, hi) at index r:
-      // m = m0 + (r&3) + 8*(r>>2) + 4*hi + 32*wave (the af B-operand
-      // rows), hidden = 64*chunk + 32*t + c. relu/dropout applied
-      // IN-PLACE on acc (a separate st[16] doubled the live range by 16
-      // registers — the difference between spilling and not).
+      // Intermediate element (m, hidden) for lane (c, hi) at index r
+      // (B1 is swapped: hidden in regs, m in lanes, see b1_step):
+      // m = m0 + 32*wave + c, hidden = 64*chunk + 32*t + 4*hi + (r&3)
+      // + 8*(r>>2). relu/dropout applied IN-PLACE on acc (a separate
+      // st[16] doubled the live range by 16 registers — the difference
+      // between spilling and not).
       if (MODE == 0) {
         const int ln2 = lane_recompute();
-        const unsigned hidx = 64 * chunk + 32 * t + (ln2 & 31);
-        const unsigned mbase = m0 + 4 * (ln2 >> 5) + 32 * wave;
+        const unsigned mrow = m0 + 32 * wave + (ln2 & 31);
+        const unsigned hbase = 64 * chunk + 32 * t + 4 * (ln2 >> 5);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           float v = acc[r] > 0.f ? acc[r] : 0.f;
           if (p > 0.f) {
-            const unsigned mrow = mbase + (r & 3) + 8 * (r >> 2);
+            const unsigned hidx = hbase + (r & 3) + 8 * (r >> 2);
             v = rand01((unsigned)seed, mrow, hidx) < p ? 0.f
                                                        : v * inv_keep;
           }
