@@ -31,8 +31,12 @@ def save_checkpoint(
     optimizer: Optional[torch.optim.Optimizer],
     params: Params,
     metrics: Optional[Dict[str, float]] = None,
+    extra: Optional[Dict] = None,
 ) -> str:
-    """Writes checkpoint-<n> plus sidecars; returns the checkpoint path."""
+    """Writes checkpoint-<n> plus sidecars; returns the checkpoint path.
+
+    extra entries are stored in the checkpoint payload next to the
+    standard keys (load_checkpoint returns the payload)."""
     os.makedirs(out_dir, exist_ok=True)
     name = f"checkpoint-{step}"
     path = os.path.join(out_dir, name + ".pt")
@@ -42,6 +46,8 @@ def save_checkpoint(
         "step": step,
         "epoch": epoch,
     }
+    if extra:
+        payload.update(extra)
     torch.save(payload, path)
     save_params_as_json(out_dir, params)
     with open(os.path.join(out_dir, "checkpoint"), "w") as f:

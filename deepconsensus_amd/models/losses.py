@@ -569,19 +569,80 @@ class YieldOverCCSMetric:
         self.yield_dc = self.yield_ccs = 0.0
 
 
+DISTILL_LOSS_IMPLS = ("torch", "fused")
+
+
+def resolve_distill_loss_impl(impl: Optional[str] = None) -> str:
+    """Flag value, else DC_DISTILL_LOSS, else torch."""
+    import os
+
+    impl = impl or os.environ.get("DC_DISTILL_LOSS") or "torch"
+    if impl not in DISTILL_LOSS_IMPLS:
+        raise ValueError(
+            f"unknown distill loss {impl!r}; choices: "
+            f"{', '.join(DISTILL_LOSS_IMPLS)}"
+        )
+    return impl
+
+
+class _FusedDistillLoss(torch.autograd.Function):
+    """ops/hip/distill_loss.hip: loss and d loss / d student logits from one
+    pass over the logits; backward scales the saved gradient."""
+
+    @staticmethod
+    def forward(ctx, teacher_logits, student_logits, temperature, kind, ext):
+        loss, grad = ext.distill_loss_fwd(
+            teacher_logits.detach().reshape(-1, 5),
+            student_logits.detach().reshape(-1, 5),
+            float(temperature), int(kind),
+        )
+        ctx.save_for_backward(grad)
+        ctx.shape = student_logits.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (grad,) = ctx.saved_tensors
+        return None, (grad_out * grad).view(ctx.shape), None, None, None
+
+
 class DistillationLoss(torch.nn.Module):
     """Temperature KL/MSE between teacher and student logits
-    (losses_and_metrics.py:1170-1213)."""
+    (losses_and_metrics.py:1170-1213).
+
+    impl "torch" is the elementwise chain below under autograd; "fused" runs
+    the distill_loss_fwd HIP kernel (fp32 CUDA logits only, same semantics)
+    and raises on anything else."""
 
     def __init__(self, temperature: float = 1.0,
-                 logit_loss: str = "kl_divergence"):
+                 logit_loss: str = "kl_divergence", impl: str = "torch"):
         super().__init__()
+        if impl not in DISTILL_LOSS_IMPLS:
+            raise ValueError(
+                f"unknown distill loss {impl!r}; choices: "
+                f"{', '.join(DISTILL_LOSS_IMPLS)}"
+            )
         self.temperature = temperature
         self.logit_loss = logit_loss
+        self.impl = impl
 
     def forward(
         self, teacher_logits: torch.Tensor, student_logits: torch.Tensor
     ) -> torch.Tensor:
+        if self.impl == "fused":
+            if not (teacher_logits.is_cuda and student_logits.is_cuda):
+                raise RuntimeError(
+                    "distill loss 'fused' is a HIP kernel and needs CUDA "
+                    "logits; use 'torch' on this device"
+                )
+            from deepconsensus_amd import ops as dc_ops
+
+            ext = dc_ops.get_ext(required=True)
+            kind = 1 if self.logit_loss == "mean_squared_error" else 0
+            return _FusedDistillLoss.apply(
+                teacher_logits.float(), student_logits.float(),
+                self.temperature, kind, ext,
+            )
         t = torch.softmax(teacher_logits / self.temperature, dim=-1)
         s = torch.softmax(student_logits / self.temperature, dim=-1)
         if self.logit_loss == "mean_squared_error":

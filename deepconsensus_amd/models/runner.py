@@ -502,6 +502,24 @@ class InferenceRunner:
         return x
 
     @torch.no_grad()
+    def logits_native(self, rows: torch.Tensor) -> torch.Tensor:
+        """Native path through the final LayerNorm and head: fp32 logits
+        [B, L, 5], what model.encode(rows, training=False)["logits"] holds.
+        The distillation teacher's forward (models/distill.py)."""
+        if not self.native:
+            raise RuntimeError(
+                "logits_native needs the native path: a CUDA device and a "
+                "learned-values model with a condenser"
+            )
+        x = self.encode_native(rows.to(self.device, non_blocking=True))
+        with trace.range("K10_ln_head_logits"):
+            logits = self.ext.ln_head_logits(
+                x.reshape(-1, x.shape[-1]), self.ln_gamma, self.ln_beta,
+                self.w_head, self.b_head,
+            )
+        return logits.view(x.shape[0], x.shape[1], 5)
+
+    @torch.no_grad()
     def forward_windows_graphed(self, host_rows: torch.Tensor):
         """Fixed-shape hipGraph-captured serving step (native path).
 

@@ -43,6 +43,71 @@ def _prepare_batch(batch, device):
     return rows, label
 
 
+class EvalMetrics:
+    """eval/per_example_accuracy and eval/yield_over_ccs over eval batches
+    (shared by the train and distill loops)."""
+
+    def __init__(self, max_passes: int):
+        self.max_passes = max_passes
+        self.acc = losses_lib.PerExampleAccuracy()
+        self.align_metric = losses_lib.AlignmentMetric()
+        self.yield_metric = losses_lib.YieldOverCCSMetric()
+
+    def update(self, rows, label, probs) -> None:
+        # Metrics run on-device when the K14 HIP kernel is
+        # available (AlignmentMetric dispatches); CPU otherwise.
+        self.acc.update_state(label, probs)
+        ccs_rows = rows[:, 4 * self.max_passes, :]
+        ic, ip = losses_lib.get_batch_identity_ccs_pred(
+            ccs_rows, probs, label, self.align_metric
+        )
+        self.yield_metric.update_state(ic, ip)
+
+    def result(self) -> dict:
+        return {
+            "eval/per_example_accuracy": self.acc.result(),
+            "eval/yield_over_ccs": self.yield_metric.result(),
+        }
+
+
+def decay_schedule_steps(params: cfg.Params, world: int):
+    """(global batch, steps per epoch, LR decay steps)."""
+    n_train = params.get("n_examples_train") or 0
+    global_batch = params.batch_size * world
+    steps_per_epoch = max(n_train // global_batch, 1)
+    decay_steps = steps_per_epoch * max(
+        params.get("num_epochs_for_decay", params.num_epochs), 1
+    )
+    return global_batch, steps_per_epoch, decay_steps
+
+
+def open_summary_writers(out_dir: str):
+    """TensorBoard-equivalent event files (model_utils.py:549-583):
+    (train, eval) writers under <out_dir>/summaries."""
+    return (
+        EventWriter(os.path.join(out_dir, "summaries", "train")),
+        EventWriter(os.path.join(out_dir, "summaries", "eval")),
+    )
+
+
+def save_eval_checkpoint(out_dir, step, epoch, model, optimizer, params,
+                         metrics, write_checkpoint_metrics, extra=None):
+    """checkpoint-<step> (+ metrics row) and the best-checkpoint update."""
+    ckpt_lib.save_checkpoint(
+        out_dir, step, epoch, model, optimizer, params,
+        metrics if write_checkpoint_metrics else None, extra=extra,
+    )
+    ckpt_lib.update_best_checkpoint(
+        out_dir, f"checkpoint-{step}",
+        metrics["eval/per_example_accuracy"],
+    )
+
+
+def write_training_summary(out_dir: str, summary: dict) -> None:
+    with open(os.path.join(out_dir, "training_summary.json"), "w") as f:
+        json.dump(summary, f, indent=2)
+
+
 def train_model(
     out_dir: str,
     params: cfg.Params,
@@ -81,11 +146,8 @@ def train_model(
         log.info("warm-started from %s", warm_start)
     comm.broadcast_parameters(model)
 
-    n_train = params.get("n_examples_train") or 0
-    global_batch = params.batch_size * world
-    steps_per_epoch = max(n_train // global_batch, 1)
-    decay_steps = steps_per_epoch * max(
-        params.get("num_epochs_for_decay", params.num_epochs), 1
+    global_batch, steps_per_epoch, decay_steps = decay_schedule_steps(
+        params, world
     )
     optimizer, schedule = lamb_lib.create_optimizer(
         params, decay_steps, model
@@ -121,9 +183,7 @@ def train_model(
 
     def run_eval() -> dict:
         model.eval()
-        acc = losses_lib.PerExampleAccuracy()
-        align_metric = losses_lib.AlignmentMetric()
-        yield_metric = losses_lib.YieldOverCCSMetric()
+        eval_metrics = EvalMetrics(params.max_passes)
         total_loss, n_batches = 0.0, 0
         with torch.no_grad():
             for rows, label in eval_ds.iterate():
@@ -133,34 +193,18 @@ def train_model(
                 )
                 total_loss += float(loss)
                 n_batches += 1
-                # Metrics run on-device when the K14 HIP kernel is
-                # available (AlignmentMetric dispatches); CPU otherwise.
-                acc.update_state(label, probs)
-                ccs_rows = rows[:, 4 * params.max_passes, :]
-                ic, ip = losses_lib.get_batch_identity_ccs_pred(
-                    ccs_rows, probs, label, align_metric
-                )
-                yield_metric.update_state(ic, ip)
+                eval_metrics.update(rows, label, probs)
         model.train()
         n = max(n_batches, 1)
-        return {
-            "eval/loss": total_loss / n,
-            "eval/per_example_accuracy": acc.result(),
-            "eval/yield_over_ccs": yield_metric.result(),
-        }
+        return {"eval/loss": total_loss / n, **eval_metrics.result()}
 
     model.train()
     summary = {}
     t0 = time.time()
     steps_this_session = 0
-    # TensorBoard-equivalent event files (model_utils.py:549-583):
-    # train/ and eval/ writers under <out_dir>/summaries.
     train_writer = eval_writer = None
     if main:
-        train_writer = EventWriter(os.path.join(out_dir, "summaries",
-                                                "train"))
-        eval_writer = EventWriter(os.path.join(out_dir, "summaries",
-                                               "eval"))
+        train_writer, eval_writer = open_summary_writers(out_dir)
     for epoch in range(initial_epoch, params.num_epochs):
         for rows, label in train_ds.iterate(epoch):
             lr = schedule.apply(optimizer, step)
@@ -211,14 +255,9 @@ def train_model(
                     metrics["eval/loss"]
                 ) / world
                 if main:
-                    name = f"checkpoint-{step}"
-                    ckpt_lib.save_checkpoint(
+                    save_eval_checkpoint(
                         out_dir, step, epoch, model, optimizer, params,
-                        metrics if write_checkpoint_metrics else None,
-                    )
-                    ckpt_lib.update_best_checkpoint(
-                        out_dir, name,
-                        metrics["eval/per_example_accuracy"],
+                        metrics, write_checkpoint_metrics,
                     )
                     log.info("eval @%d: %s", step, metrics)
                     eval_writer.add_scalars(step, metrics)
@@ -233,13 +272,9 @@ def train_model(
     # Final eval + checkpoint.
     metrics = run_eval()
     if main:
-        ckpt_lib.save_checkpoint(
+        save_eval_checkpoint(
             out_dir, step, params.num_epochs - 1, model, optimizer, params,
-            metrics if write_checkpoint_metrics else None,
-        )
-        ckpt_lib.update_best_checkpoint(
-            out_dir, f"checkpoint-{step}",
-            metrics["eval/per_example_accuracy"],
+            metrics, write_checkpoint_metrics,
         )
     summary = metrics
     summary["steps"] = step
@@ -247,8 +282,7 @@ def train_model(
         eval_writer.add_scalars(step, metrics)
         train_writer.close()
         eval_writer.close()
-        with open(os.path.join(out_dir, "training_summary.json"), "w") as f:
-            json.dump(summary, f, indent=2)
+        write_training_summary(out_dir, summary)
     return summary
 
 

@@ -39,6 +39,7 @@ _SRCS = [
     os.path.join(_OPS_DIR, "hip", "cigar_expand.hip"),
     os.path.join(_OPS_DIR, "hip", "fused_outproj_ffn.hip"),
     os.path.join(_OPS_DIR, "hip", "batch_assemble.hip"),
+    os.path.join(_OPS_DIR, "hip", "distill_loss.hip"),
 ]
 EXT_NAME = "dc_hip_kernels"
 

@@ -353,8 +353,30 @@ void batch_assemble_into(at::Tensor pool, at::Tensor upload, int64_t n_in,
                          bool remove_label_gaps);
 void pool_store(at::Tensor pool, at::Tensor upload, at::Tensor scatter);
 int64_t batch_assemble_slot_floats(int64_t R, int64_t L);
+// Defined in distill_loss.hip.
+at::Tensor ln_head_logits(at::Tensor x, at::Tensor gamma, at::Tensor beta,
+                          at::Tensor w_head, at::Tensor b_head,
+                          c10::optional<at::Tensor> out);
+std::vector<at::Tensor> distill_loss_fwd(at::Tensor teacher_logits,
+                                         at::Tensor student_logits,
+                                         double temperature, int64_t kind,
+                                         c10::optional<at::Tensor> grad_out);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("ln_head_logits", &ln_head_logits,
+        "Final LayerNorm + Dense(5) head -> fp32 logits [N, 5] (the "
+        "teacher's encode()[\"logits\"] on the serving path); out, if "
+        "given, receives them",
+        pybind11::arg("x"), pybind11::arg("gamma"), pybind11::arg("beta"),
+        pybind11::arg("w_head"), pybind11::arg("b_head"),
+        pybind11::arg("out") = pybind11::none());
+  m.def("distill_loss_fwd", &distill_loss_fwd,
+        "Distillation loss (K17) in one pass: temperature softmaxes, KL "
+        "(kind 0) or MSE (kind 1) mean over positions, and d loss / d "
+        "student logits -> (loss, grad_student); fixed-order reduction",
+        pybind11::arg("teacher_logits"), pybind11::arg("student_logits"),
+        pybind11::arg("temperature"), pybind11::arg("kind"),
+        pybind11::arg("grad_out") = pybind11::none());
   m.def("batch_assemble_into", &batch_assemble_into,
         "Device training input: gather examples out of the HBM shuffle pool "
         "or this step's upload, clip PW/IP/SN rows, optionally left-shift "
